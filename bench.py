@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark: stereo frames/s of the MI355X VO hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (N > 1)
 
 Workload (BASELINE.json configs[1]): 960x600 synthetic forest stereo along the 1018_00
@@ -17,7 +17,11 @@ points3D, dist.exchange_frame_map, placed on the device by dist.GlobalMap), plus
 barrier / max-over-ranks.  `--gpus N` without WORLD_SIZE starts the N ranks itself
 (torch.distributed.run, 127.0.0.1) before any GPU call.
 
-Prints ONE JSON line (rank 0).  See DESIGN.md §Measurement for the roofline definition.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the
+headline figure.  ``--full`` adds every other leg to that line: the per-kernel breakdown pre-pass
+and the roofline of the dominant kernel, the ATE / RPE runs with
+their CPU reference chain, and the CPU baseline.  ``--dump-outputs DIR`` writes what the last
+timed step returned (``dump_outputs``) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -308,6 +312,43 @@ def pmc_valu(shape: str):
                         for r in rows if r["kernel"].startswith(hot)}}
 
 
+DUMP_DISPARITY_SAMPLES = 1 << 20
+
+
+def dump_outputs(path: str, fe, T: torch.Tensor, st: torch.Tensor) -> dict:
+    """--dump-outputs: the arrays the caller of the last timed step received, as path/<name>.npy
+    (float64 / float32; a few MB): the step's return value -- ``T`` (the BA-refined relative
+    transforms, or the PnP ones without local BA) and ``status`` -- and the front end's per-step
+    result buffers a caller reads beside it: ``T_pnp``, ``n_points`` and ``points3d`` (the
+    exchange sends these), ``n_matches`` (left), and ``disparity``, a fixed seeded sample of
+    the step's int16 disparity maps at the flat indices ``disparity_index``.  Entries the
+    library leaves unwritten are zeroed, so two builds compare array for array: points past
+    ``n_points``, and the transforms of frames with a negative status (no pose)."""
+    os.makedirs(path, exist_ok=True)
+    n = T.shape[0]
+    posed = (st[:n] >= 0)
+    npts = fe.npts[:n].clamp(min=0)
+    live = torch.arange(fe.cap, device=fe.dev)[None, :] < npts[:, None]
+    disp = fe.disp[:n].reshape(-1)
+    idx = np.sort(np.random.default_rng(0).integers(0, disp.numel(), size=min(DUMP_DISPARITY_SAMPLES, disp.numel())))
+    arrays = {
+        "T": torch.where(posed[:, None, None], T, torch.zeros_like(T)).to(torch.float64),
+        "status": st[:n].to(torch.float32),
+        "T_pnp": torch.where(posed[:, None, None], fe.T[:n], torch.zeros_like(fe.T[:n])).to(torch.float64),
+        "n_points": fe.npts[:n].to(torch.float32),
+        "points3d": torch.where(live[:, :, None], fe.P3[:n], torch.zeros_like(fe.P3[:n])).to(torch.float32),
+        "n_matches": fe.nmatch[:n].to(torch.float32),
+        "disparity": disp[torch.as_tensor(idx, device=fe.dev)].to(torch.float32),
+        "disparity_index": torch.as_tensor(idx.astype(np.float64)),
+    }
+    total = 0
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "arrays": sorted(arrays), "bytes": total}
+
+
 def exchange_fields(world: int, rank0_only: bool, send_bytes: int, stream_ms, collective_ms, host_ms, steps) -> dict:
     """The JSON line's multi-rank exchange record: what each rank sends and
     receives per step and how long the side stream spends on it (send copies + collectives +
@@ -537,6 +578,12 @@ def main():
                          "frames: ONE sequence of steps x B frames split by frame pairs over the GPUs (strong scaling)")
     ap.add_argument("--map-rank0", type=int, default=0,
                     help="multi-rank map on rank 0 only (gather) instead of on every rank (all-gather, the default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure: per-kernel breakdown pass + roofline, "
+                         "ATE / RPE runs with the CPU reference chain, CPU baseline (--ate-frames, --cpu-ate, "
+                         "--cpu-frames apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned as DIR/<name>.npy (rank 0)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / process-group check without a GPU (gloo ranks on the CPU, no VO work)")
     args = ap.parse_args()
@@ -582,37 +629,40 @@ def main():
     steps_total = max(args.warmup, 1) + 2 + args.steps
     rank_step = fdist.SequenceRank(fe, map_capacity=steps_total * world * B * fe.cap, map_rank0_only=bool(args.map_rank0))
     nstep = [0]
+    last = [None]  # what the latest step returned
 
     def eager_step():
         Lb, Rb = fwd if nstep[0] % 2 == 0 else bwd
         nstep[0] += 1
-        rank_step.step(Lb, Rb)
+        last[0] = rank_step.step(Lb, Rb)
 
     step = eager_step
     for _ in range(max(args.warmup, 1)):
         step()
     torch.cuda.synchronize()
 
-    # per-kernel breakdown (separate pass, every launch bracketed by events).  SGBM runs in
-    # order on the main stream here, so no kernel's time includes another stream's kernels
-    # (the timed region below keeps the overlapped schedule).
-    fe.ctx.timing_enable(None)
-    ov = fe.overlap_sgbm
-    fe.overlap_sgbm = False
-    nprof = 2
-    for _ in range(nprof):
-        eager_step()
-    torch.cuda.synchronize()
-    fe.overlap_sgbm = ov
-    stages = fe.ctx.timing_read()
-    fe.ctx.timing_enable([])
-    dom = max(stages, key=lambda k: stages[k][0])
-    stage_ms = {k: round(v[0] / nprof, 4) for k, v in sorted(stages.items(), key=lambda kv: -kv[1][0])}
+    stages, dom, stage_ms = {}, None, None
+    if args.full:
+        # per-kernel breakdown (separate pass, every launch bracketed by events).  SGBM runs in
+        # order on the main stream here, so no kernel's time includes another stream's kernels
+        # (the timed region below keeps the overlapped schedule).
+        fe.ctx.timing_enable(None)
+        ov = fe.overlap_sgbm
+        fe.overlap_sgbm = False
+        nprof = 2
+        for _ in range(nprof):
+            eager_step()
+        torch.cuda.synchronize()
+        fe.overlap_sgbm = ov
+        stages = fe.ctx.timing_read()
+        fe.ctx.timing_enable([])
+        dom = max(stages, key=lambda k: stages[k][0])
+        stage_ms = {k: round(v[0] / nprof, 4) for k, v in sorted(stages.items(), key=lambda kv: -kv[1][0])}
 
-    # timed region: only the dominant kernel bracketed (2 events per launch); with the SGBM
-    # stream overlapped its launches share the GPU with the main stream's kernels, so the
-    # in-order launch time of the breakdown pass is reported beside it
-    fe.ctx.timing_enable([dom])
+        # timed region: only the dominant kernel bracketed (2 events per launch); with the SGBM
+        # stream overlapped its launches share the GPU with the main stream's kernels, so the
+        # in-order launch time of the breakdown pass is reported beside it
+        fe.ctx.timing_enable([dom])
     rank_step.timing(True)
     rk.barrier()
     torch.cuda.synchronize()
@@ -622,9 +672,12 @@ def main():
     torch.cuda.synchronize()
     rk.barrier()
     elapsed = time.perf_counter() - t0
-    dom_t = fe.ctx.timing_read()
+    dom_t = fe.ctx.timing_read() if args.full else {}
     fe.ctx.timing_enable([])
     elapsed = rk.max_elapsed(elapsed)
+    dumped = None
+    if args.dump_outputs and rank == 0 and last[0] is not None:
+        dumped = dump_outputs(args.dump_outputs, fe, last[0][0], last[0][1])
     # SGBM pairs dropped by an L-path hand-off timeout in the last two steps (fvo_sgbm's status
     # of the two front-stage slots; the classic schedule cannot time out)
     sg_failed = int(sum(int((t == _lib.SGBM_HANDOFF_TIMEOUT).sum().item()) for t in fe.sg_status_buf))
@@ -646,19 +699,33 @@ def main():
                               "fvo_chain_poses + fvo_map_transform)"}
     frames = world * B * args.steps
     value = frames / elapsed
-    dom_ms, dom_launches = dom_t.get(dom, (0.0, 0))
-    avg_launch_s = dom_ms / max(dom_launches, 1) / 1e3
-    io_ms, io_launches = stages.get(dom, (0.0, 0))
-    avg_launch_io_s = io_ms / max(io_launches, 1) / 1e3
-    frames_per_launch = B  # every kernel of the step processes the whole batch in one launch
-    bpf = algorithmic_bytes_per_frame(W, H, args.nfeatures)
-    achieved = bpf * frames_per_launch / avg_launch_s / 1e9 if avg_launch_s > 0 else 0.0
     shape = shape_key(W, H, args.nfeatures, B, args.ba_window)
-    traffic, traffic_src = pmc_traffic(dom, shape)
-    traffic_rate = traffic / avg_launch_s / 1e9 if (traffic and avg_launch_s > 0) else None
+    roofline = None
+    if args.full:
+        dom_ms, dom_launches = dom_t.get(dom, (0.0, 0))
+        avg_launch_s = dom_ms / max(dom_launches, 1) / 1e3
+        io_ms, io_launches = stages.get(dom, (0.0, 0))
+        avg_launch_io_s = io_ms / max(io_launches, 1) / 1e3
+        frames_per_launch = B  # every kernel of the step processes the whole batch in one launch
+        bpf = algorithmic_bytes_per_frame(W, H, args.nfeatures)
+        achieved = bpf * frames_per_launch / avg_launch_s / 1e9 if avg_launch_s > 0 else 0.0
+        traffic, traffic_src = pmc_traffic(dom, shape)
+        traffic_rate = traffic / avg_launch_s / 1e9 if (traffic and avg_launch_s > 0) else None
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
+                    "traffic": traffic, "traffic_source": traffic_src,
+                    "traffic_rate_gbs": round(traffic_rate, 1) if traffic_rate else None,
+                    "traffic_frac": round(traffic_rate / HBM_PEAK_GBS, 4) if traffic_rate else None,
+                    "algorithmic_bytes_per_frame": bpf, "frames_per_launch": frames_per_launch,
+                    "avg_launch_ms": round(avg_launch_s * 1e3, 4),
+                    "avg_launch_ms_in_order": round(avg_launch_io_s * 1e3, 4),
+                    "achieved_in_order": round(bpf * frames_per_launch / avg_launch_io_s / 1e9, 3)
+                    if avg_launch_io_s > 0 else None,
+                    "traffic_rate_gbs_in_order": round(traffic / avg_launch_io_s / 1e9, 1)
+                    if (traffic and avg_launch_io_s > 0) else None}
 
     ate = None
-    if rank == 0 and args.ate_frames > 1:
+    if args.full and rank == 0 and args.ate_frames > 1:
         aseq = synth.StereoSequence(seed=100, n_frames=args.ate_frames, W=W, H=H, device=dev)
         La, Ra = aseq.frames(range(aseq.n))
         afe = vo.StereoFrontEnd(W, H, aseq.K, synth.DIST_L, synth.BASELINE, batch=min(B, 32),
@@ -692,7 +759,7 @@ def main():
                                     "gpu_pnp_only_rel_diff": round(abs(gpu_pnp - ref["rmse_m"]) / ref["rmse_m"], 6)}
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_frames > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_frames > 0:
         cpu = cpu_baseline(args.cpu_frames, args.nfeatures, W, H, args.ba_window)
         # per-frame stage times beside the GPU's (in-order breakdown pass / B; ORB: the CPU path
         # extracts 4 images per frame as the reference does, the GPU path 2)
@@ -737,21 +804,11 @@ def main():
                        "local_ba": (f"window K={args.ba_window} per frame, 10 LM iterations (fvo_ba_windows)"
                                     if args.ba_window else "off"),
                        "parallelism": f"seq-per-gpu x{world}"},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "traffic_rate_gbs": round(traffic_rate, 1) if traffic_rate else None,
-                         "traffic_frac": round(traffic_rate / HBM_PEAK_GBS, 4) if traffic_rate else None,
-                         "algorithmic_bytes_per_frame": bpf, "frames_per_launch": frames_per_launch,
-                         "avg_launch_ms": round(avg_launch_s * 1e3, 4),
-                         "avg_launch_ms_in_order": round(avg_launch_io_s * 1e3, 4),
-                         "achieved_in_order": round(bpf * frames_per_launch / avg_launch_io_s / 1e9, 3)
-                         if avg_launch_io_s > 0 else None,
-                         "traffic_rate_gbs_in_order": round(traffic / avg_launch_io_s / 1e9, 1)
-                         if (traffic and avg_launch_io_s > 0) else None},
+            "full": bool(args.full),  # False: the legs below that only --full runs are null
+            "roofline": roofline,
             "cpu_baseline": cpu,
-            "ba_mfma": pmc_mfma(shape) if args.ba_window else None,
-            "valu": pmc_valu(shape),
+            "ba_mfma": pmc_mfma(shape) if (args.full and args.ba_window) else None,
+            "valu": pmc_valu(shape) if args.full else None,
             "pmc_shape": shape,
             "ate": ate,
             "global_map": global_map,
@@ -759,6 +816,7 @@ def main():
             "stages_ms_per_step": stage_ms,
             "sgbm": {"mode": args.sgbm_mode, "pairs_failed_last_2_steps": sg_failed},
             "workspace_gb": round(fe.ctx.workspace_bytes / 1e9, 2),
+            "dumped_outputs": dumped,
         }
         out.update(rk.fields())
         print(json.dumps(out), flush=True)

@@ -10,5 +10,5 @@ for sh in 600 1080; do
   timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof$sh -o run -- python tools/bench_ba.py $flag > gpurun_out/ba/prof$sh.log 2>&1 || exit 1
   find /tmp/prof$sh -name "*kernel_stats.csv" -exec cp {} gpurun_out/ba/kstats_$sh.csv \;
 done
-[ -n "$WITH_BENCH" ] && { timeout -k 10 240 python bench.py --steps 20 --warmup 5 --cpu-frames 0 > gpurun_out/ba/bench_full.log 2>&1 || exit 1; }
+[ -n "$WITH_BENCH" ] && { timeout -k 10 240 python bench.py --full --steps 20 --warmup 5 --cpu-frames 0 > "${BENCH_LOG:-/tmp/bench_full.log}" 2>&1 || exit 1; }
 exit 0
