@@ -79,6 +79,8 @@ SIGNATURES = {
     "fvo_count_guard": (ctypes.c_int, [_P, _P, _P, _I, _I, _P, _I, _P, _P]),
     "fvo_voxel_workspace_bytes": (ctypes.c_int64, [_L]),
     "fvo_voxel_down_sample": (ctypes.c_int, [_P, _P, _L, ctypes.c_double, _P, _L, _P, _P, _P, _P]),
+    "fvo_speckle_workspace_bytes": (ctypes.c_int64, [_I, _I, _I]),
+    "fvo_filter_speckles": (ctypes.c_int, [_P, _P, _I, _I, _I, _L, _I, _I, _I, _I, _P, _L, _P]),
     "fvo_motion_blur": (ctypes.c_int, [_P, _P, _I, _L, _I, _I, ctypes.c_double, _P, _P, _I, _P, _P, _L, _I, _P]),
     "fvo_test_retain_best": (ctypes.c_int, [_P, _P, _I, _I, _P, _P, _P]),
     "fvo_debug_buffer": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
@@ -490,6 +492,38 @@ class Context:
         self._check(self.L.fvo_voxel_down_sample(self.h, _ptr(points), n, float(voxel_size), _ptr(workspace), wb,
                                                  _ptr(out), _ptr(cnt), _ptr(status), _stream(self.device)))
         return out, cnt, status
+
+    def speckle_workspace_bytes(self, batch: int, height: int, width: int) -> int:
+        """fvo_speckle_workspace_bytes: scratch bytes of filter_speckles for [batch, height, width]."""
+        wb = int(self.L.fvo_speckle_workspace_bytes(int(batch), int(height), int(width)))
+        if wb < 0:
+            raise ValueError(f"filter_speckles: unsupported size batch={batch} {width}x{height}")
+        return wb
+
+    def filter_speckles(self, disp, new_val, max_speckle_size, max_diff, workspace=None):
+        """cv2.filterSpeckles on int16 [B,H,W] (or [H,W]) device disparity maps, in place
+        (fvo_filter_speckles); returns disp.  disp may be a column range of a wider buffer (row
+        pitch > W); rows must be element-contiguous.  workspace: uint8 device tensor of at least
+        speckle_workspace_bytes(B, H, W) bytes, allocated here only when none is passed."""
+        if disp.dtype != torch.int16 or disp.dim() not in (2, 3):
+            raise TypeError("disp must be int16 [B,H,W] or [H,W]")
+        d3 = disp if disp.dim() == 3 else disp[None]
+        B, H, W = d3.shape
+        if B == 0 or H == 0 or W == 0:
+            return disp
+        if W > 1 and d3.stride(2) != 1:
+            raise ValueError("filter_speckles: the last dimension must be contiguous")
+        pitch = d3.stride(1) if H > 1 else W
+        istride = d3.stride(0) if B > 1 else pitch * H
+        wb = self.speckle_workspace_bytes(B, H, W)
+        if workspace is None:
+            workspace = torch.empty((max(wb, 1),), dtype=torch.uint8, device=self.device)
+        elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < wb:
+            raise ValueError(f"filter_speckles: workspace must be a contiguous uint8 tensor of >= {wb} bytes")
+        self._check(self.L.fvo_filter_speckles(self.h, _ptr(d3), B, H, W, istride, pitch, int(new_val),
+                                               int(max_speckle_size), int(max_diff), _ptr(workspace),
+                                               workspace.numel(), _stream(self.device)))
+        return disp
 
     def gather_matches(self, kp0, kp1, matches, nmatch, out=None):
         """mkpts0/mkpts1 of a BF match list (fvo_gather_matches): (p0 f32[B,cap,2], p1, n i32[B])."""

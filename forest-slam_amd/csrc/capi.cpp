@@ -411,7 +411,8 @@ const char* fvo_kernel_name(int id) {
       "orb_copy_level0", "orb_resize", "orb_fast_score", "orb_nms_count", "orb_row_scan", "orb_nms_compact",
       "orb_select_fast", "orb_harris", "orb_select_harris", "orb_offsets", "orb_angle", "orb_blur", "orb_brief",
       "bf_argmin", "bf_finish", "sgbm_vert", "sgbm_rows", "sgbm_median", "backproject",
-      "pnp_ransac", "ba_stereo", "ba_build", "ba_solve", "gather_matches", "essential_ransac", "recover_pose", "ingest_undistort_gray", "motion_blur", "map_transform", "voxel_down_sample"};
+      "pnp_ransac", "ba_stereo", "ba_build", "ba_solve", "gather_matches", "essential_ransac", "recover_pose", "ingest_undistort_gray", "motion_blur", "map_transform", "voxel_down_sample",
+      "speckle_local", "speckle_seams", "speckle_sum", "speckle_apply"};
   return (id >= 0 && id < KN_COUNT) ? names[id] : "";
 }
 

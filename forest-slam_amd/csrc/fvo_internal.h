@@ -40,7 +40,8 @@ enum FvoKernel {
   KN_ORB_COPY, KN_ORB_RESIZE, KN_ORB_FAST, KN_ORB_NMS_COUNT, KN_ORB_ROW_SCAN, KN_ORB_COMPACT, KN_ORB_SELECT1,
   KN_ORB_HARRIS, KN_ORB_SELECT2, KN_ORB_OFFSETS, KN_ORB_ANGLE, KN_ORB_BLUR, KN_ORB_BRIEF, KN_BF_ARGMIN,
   KN_BF_FINISH, KN_SG_VERT, KN_SG_ROWS, KN_SG_MEDIAN, KN_BACKPROJECT, KN_PNP, KN_BA_STEREO,
-  KN_BA_BUILD, KN_BA_SOLVE, KN_GATHER, KN_ESSENTIAL, KN_RECOVER, KN_INGEST, KN_MOTION_BLUR, KN_MAP_XFORM, KN_VOXEL, KN_COUNT
+  KN_BA_BUILD, KN_BA_SOLVE, KN_GATHER, KN_ESSENTIAL, KN_RECOVER, KN_INGEST, KN_MOTION_BLUR, KN_MAP_XFORM, KN_VOXEL,
+  KN_SPK_LOCAL, KN_SPK_SEAMS, KN_SPK_SUM, KN_SPK_APPLY, KN_COUNT
 };
 
 struct TimingRec {
@@ -185,6 +186,10 @@ int count_guard_run(fvo_ctx* ctx, const int32_t* cnt, const int32_t* q_cnt, int 
 int64_t voxel_workspace_bytes(int64_t n);
 int voxel_run(fvo_ctx* ctx, const double* pts, int64_t n, double voxel, void* ws, size_t ws_bytes, double* out,
               int32_t* n_out, int32_t* status, hipStream_t s);
+// Speckle filter (speckle.hip); arguments validated by speckle_api.cpp.  ws: two int32 planes
+// [batch][H*W] (fvo_speckle_workspace_bytes).
+int speckle_run(fvo_ctx* ctx, int16_t* disp, int batch, int H, int W, int64_t image_stride, int pitch, int new_val,
+                int max_speckle_size, int max_diff, void* ws, hipStream_t s);
 int mono_init(fvo_ctx* ctx);
 int gather_run(fvo_ctx* ctx, const float* kp0, const float* kp1, const int32_t* matches, const int32_t* nmatch,
                int batch, int cap, float* p0, float* p1, int32_t* npts, hipStream_t s);

@@ -7,6 +7,7 @@ Face 1 mirrors the OpenCV calls of ros_ws/src/stereo_slam.py:
     kps, desc = orb.detectAndCompute(img, None)                 (:232-233, :240-241)
     matches = bf.match(desc0, desc1)                            (:234, :242)
     StereoSGBM_create(...).compute(L, R)                        (:108-117)
+      (with OpenCV's speckleWindowSize / speckleRange post-filter, and filterSpeckles itself)
     ok, rvec, tvec, inliers = solvePnPRansac(P, p, K, dist, ...)  (:294-295)
     R, _ = Rodrigues(rvec)                                      (:298)
 and of ros_ws/src/mono_slam.py:
@@ -200,13 +201,17 @@ class StereoSGBM:
                  uniquenessRatio=0, speckleWindowSize=0, speckleRange=0, mode=STEREO_SGBM_MODE_SGBM):
         if mode != STEREO_SGBM_MODE_SGBM_3WAY:
             raise NotImplementedError("StereoSGBM: only mode=STEREO_SGBM_MODE_SGBM_3WAY is implemented")
-        if blockSize != 7 or numDisparities not in (64, 96, 128) or uniquenessRatio != 0 or speckleWindowSize != 0:
+        if blockSize != 7 or numDisparities not in (64, 96, 128) or uniquenessRatio != 0:
             raise NotImplementedError("StereoSGBM: implemented for blockSize=7, numDisparities in {64, 96, 128}, "
-                                      "uniquenessRatio=0, speckleWindowSize=0")
+                                      "uniquenessRatio=0 (any speckleWindowSize / speckleRange)")
         self.params = dict(min_disparity=int(minDisparity), num_disparities=int(numDisparities),
                            block_size=int(blockSize), P1=int(P1), P2=int(P2), disp12_max_diff=int(disp12MaxDiff),
                            pre_filter_cap=int(preFilterCap), uniqueness_ratio=int(uniquenessRatio))
+        # StereoSGBM::compute: filterSpeckles(disp, (minDisparity - 1) * 16, speckleWindowSize,
+        # 16 * speckleRange) after the median, when speckleWindowSize > 0
+        self.speckle_window, self.speckle_range = int(speckleWindowSize), int(speckleRange)
         self._cache = _CtxCache()
+        self._speckle_ws = _CtxCache()
 
     def computeDevice(self, left, right) -> torch.Tensor:
         L, R = _u8_image(left, "left"), _u8_image(right, "right")
@@ -215,7 +220,13 @@ class StereoSGBM:
         H, W = L.shape
         ctx = self._cache.get((W, H), lambda: _lib.Context(W, H, max_batch=1, stages=_lib.STAGE_SGBM,
                                                            **self.params))
-        return ctx.sgbm(L, R)[0]
+        disp = ctx.sgbm(L, R)
+        if self.speckle_window > 0:
+            ws = self._speckle_ws.get((W, H), lambda: torch.empty((ctx.speckle_workspace_bytes(1, H, W),),
+                                                                  dtype=torch.uint8, device=ctx.device))
+            ctx.filter_speckles(disp, (self.params["min_disparity"] - 1) * 16, self.speckle_window,
+                                16 * self.speckle_range, workspace=ws)
+        return disp[0]
 
     def compute(self, left, right, disparity=None):
         return self.computeDevice(left, right).cpu().numpy()
@@ -257,6 +268,42 @@ def StereoSGBM_create(minDisparity=0, numDisparities=16, blockSize=3, P1=0, P2=0
                       uniquenessRatio=0, speckleWindowSize=0, speckleRange=0, mode=STEREO_SGBM_MODE_SGBM):
     return StereoSGBM(minDisparity, numDisparities, blockSize, P1, P2, disp12MaxDiff, preFilterCap, uniquenessRatio,
                       speckleWindowSize, speckleRange, mode)
+
+
+_speckle_cache = _CtxCache()
+
+
+def filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf=None):
+    """cv2.filterSpeckles(img, newVal, maxSpeckleSize, maxDiff[, buf]) -> (img, buf) for CV_16SC1
+    disparity maps, filtered in place on the GPU (fvo_filter_speckles).  img: a NumPy int16
+    (H, W) array (uploaded, filtered, written back into the same array, as cv2 does), or an int16
+    torch tensor [H,W] / [B,H,W] (moved to the device if it is not there).  buf: the scratch
+    tensor a previous call returned (reused when large enough).  8-bit input is not implemented."""
+    is_np = not isinstance(img, torch.Tensor)
+    t = torch.from_numpy(img) if is_np else img
+    if t.dtype == torch.uint8:
+        raise NotImplementedError("filterSpeckles: only CV_16SC1 (int16) images are implemented")
+    if t.dtype != torch.int16 or t.dim() not in (2, 3) or (is_np and t.dim() != 2):
+        raise error(f"filterSpeckles: expected an int16 single-channel image, got {t.dtype} {tuple(t.shape)}")
+    if not -32768 <= int(newVal) <= 32767:
+        raise error("filterSpeckles: newVal outside the int16 range")
+    dev = _device()
+    d = t.to(dev) if t.device != dev else t
+    if is_np or d is not t:
+        d = d.contiguous()
+    B = d.shape[0] if d.dim() == 3 else 1
+    H, W = d.shape[-2:]
+    nb = 1 << max(0, (B - 1).bit_length())
+    ctx = _speckle_cache.get(nb, lambda: _lib.Context(64, 64, max_batch=nb, stages=_lib.STAGE_BF, kp_capacity=64))
+    if t.numel():
+        wb = ctx.speckle_workspace_bytes(B, H, W)
+        if not (isinstance(buf, torch.Tensor) and buf.dtype == torch.uint8 and buf.device == dev
+                and buf.is_contiguous() and buf.numel() >= wb):
+            buf = torch.empty((wb,), dtype=torch.uint8, device=dev)
+        ctx.filter_speckles(d, int(newVal), int(maxSpeckleSize), int(maxDiff), workspace=buf)
+        if d is not t:
+            t.copy_(d)  # (a NumPy array shares t's memory: filtered in place)
+    return img, buf
 
 
 # --------------------------------------------------------------------------- solvePnPRansac

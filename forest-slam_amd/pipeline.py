@@ -71,8 +71,10 @@ def _upload(msgs, dev):
 
 def run_stereo_bag(path: str, batch: int = 32, nfeatures: int = 500, frame_interval: int = 1, ba_window: int = 0,
                    device="cuda:0", K_left=K0, dist_left=DIST_L, K_right=K1, dist_right=DIST_R, baseline=BASELINE,
-                   point_map=None):
+                   point_map=None, speckle_window: int = 0, speckle_range: int = 0):
     """stereo_slam.py's ORB branch over a bag -> (TUM rows f64[n,8], relative T, statuses).
+    speckle_window / speckle_range: StereoSGBM_create's speckleWindowSize / speckleRange (0 = off,
+    the reference's get_disparity_map()).
     point_map: a ``mapping.PointMap`` that receives every posed frame's points3D in the map
     frame (stereo_slam.py:308-318)."""
     bag = rosbag.Bag(path)
@@ -81,7 +83,7 @@ def run_stereo_bag(path: str, batch: int = 32, nfeatures: int = 500, frame_inter
         return np.zeros((0, 8)), np.zeros((0, 4, 4)), np.zeros((0,), np.int32)
     H, W = pairs[0][1].height, pairs[0][1].width
     fe = vo.StereoFrontEnd(W, H, K_left, dist_left, baseline, batch=batch, nfeatures=nfeatures, device=device,
-                           ba_window=ba_window)
+                           ba_window=ba_window, speckle_window=speckle_window, speckle_range=speckle_range)
     ctx, dev = fe.ctx, fe.dev
 
     def gray(lo, hi):

@@ -39,7 +39,7 @@ class StereoFrontEnd:
     def __init__(self, width: int, height: int, K: np.ndarray, dist: np.ndarray, baseline: float, batch: int,
                  nfeatures: int = 500, match_right: bool = True, device=None, ba_window: int = 10,
                  ba_iters: int = 10, overlap_sgbm: bool = False, sgbm_last: bool = False, births_ahead: bool = False,
-                 **params):
+                 speckle_window: int = 0, speckle_range: int = 0, **params):
         self.B = batch
         self.K = np.asarray(K, np.float64)
         self.dist = np.resize(np.asarray(dist, np.float64), 5)
@@ -76,6 +76,13 @@ class StereoFrontEnd:
         self.disp_buf = two((B, height, width), torch.int16)
         self.sg_status_buf = two((B,), torch.int32)
         self.sgbm_can_fail = int(self.ctx.cfg.sgbm_mode) == _lib.SGBM_LPATH
+        # StereoSGBM_create(speckleWindowSize=, speckleRange=): cv2.filterSpeckles on the step's
+        # disparity maps right after SGBM (0 = off, the reference's setting: no launch).  Its
+        # scratch is used on the front stage's stream only, so one allocation serves both slots.
+        self.speckle_window, self.speckle_range = int(speckle_window), int(speckle_range)
+        self.speckle_new_val = (int(self.ctx.cfg.min_disparity) - 1) * 16
+        self.speckle_ws = (torch.empty((self.ctx.speckle_workspace_bytes(B, height, width),), dtype=torch.uint8,
+                                       device=dev) if self.speckle_window > 0 else None)
         # the BA's per-keypoint stereo points of the step's previous-left frames, computed in the
         # front stage (they need only its disparities and keypoints) into a slot like disp
         self.kstereo_buf = two((B, cap, 4), torch.float32) if self.ba_window else [None, None]
@@ -191,7 +198,7 @@ class StereoFrontEnd:
             ctx.copy_regions(self._sgbm_pairs(L, R, n) + [(self.imgs[:n], L), (self.imgs[n:2 * n], R)])
             # SGBM first: ORB + BF first measured slower (r3 4242 vs 4284, r4 5051 vs 5227 frames/s)
             if not self.sgbm_last:
-                disp = ctx.sgbm(self.prevL[:n], self.prevR[:n], out=self.disp[:n], status=self.sg_status[:n])
+                disp = self._sgbm(n)
             kp, desc, cnt = ctx.orb(self.imgs[:2 * n], out=(self.kp[:2 * n], self.desc[:2 * n], self.cnt[:2 * n]))
             # query (previous) sets: left frames then right frames; previous-left keypoints
             ctx.copy_regions([(self.q_desc[0], self.last_desc[0]), (self.q_cnt[0:1], self.last_cnt[0:1]),
@@ -207,7 +214,7 @@ class StereoFrontEnd:
                               (self.last_desc[1], desc[2 * n - 1]), (self.last_cnt[0:1], cnt[n - 1:n]),
                               (self.last_cnt[1:2], cnt[2 * n - 1:2 * n])])
             if self.sgbm_last:
-                disp = ctx.sgbm(self.prevL[:n], self.prevR[:n], out=self.disp[:n], status=self.sg_status[:n])
+                disp = self._sgbm(n)
             if self.ba_window:  # (a negative count -- ORB overflow -- reads as no keypoints)
                 ctx.keypoint_stereo(disp[:n], self.q_kp[:n], self.q_cnt[:n], self.K, self.baseline,
                                     out=self.kstereo[:n])
@@ -239,6 +246,15 @@ class StereoFrontEnd:
             self.main_done[slot] = main.record_event()
         self.k += 1
         return out, st
+
+    def _sgbm(self, n):
+        """SGBM of the step's previous pairs, then the speckle filter when it is enabled
+        (StereoSGBM::compute's order), on the current stream."""
+        disp = self.ctx.sgbm(self.prevL[:n], self.prevR[:n], out=self.disp[:n], status=self.sg_status[:n])
+        if self.speckle_window > 0:
+            self.ctx.filter_speckles(disp, self.speckle_new_val, self.speckle_window, 16 * self.speckle_range,
+                                     workspace=self.speckle_ws)
+        return disp
 
     def _sgbm_pairs(self, L, R, n):
         """Copy list for SGBM's previous pairs (the last pair of the previous step, then

@@ -34,6 +34,7 @@
  *                              float32 packing: stereo_slam.py:308-318; mono_slam.py:148; gt_mapping.py
  *   fvo_voxel_down_sample   <- open3d PointCloud.voxel_down_sample(voxel_size=0.5)
  *                              mono_slam.py:151-155, gt_mapping.py:62-66
+ *   fvo_filter_speckles     <- cv2.filterSpeckles / StereoSGBM_create(speckleWindowSize=, speckleRange=)
  *
  * Conventions
  *  - All array pointers are DEVICE pointers owned by the caller (e.g. torch tensors'
@@ -340,6 +341,24 @@ int fvo_count_guard(fvo_ctx* ctx, const int32_t* counts, const int32_t* q_counts
 int64_t fvo_voxel_workspace_bytes(int64_t n_points);
 int fvo_voxel_down_sample(fvo_ctx* ctx, const double* points, int64_t n_points, double voxel_size, void* workspace,
                           int64_t workspace_bytes, double* out, int32_t* n_out, int32_t* status, fvo_stream stream);
+
+/* cv2.filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) on `batch` CV_16SC1 disparity maps, in
+ * place (any stage; any image size, not tied to the context's).  Two 4-neighbours are connected
+ * when both differ from new_val and |int(p) - int(q)| <= max_diff; every pixel of a connected
+ * region of at most max_speckle_size pixels becomes new_val, every other pixel is untouched.
+ * StereoSGBM::compute applies it after the median when speckleWindowSize > 0, as
+ * (disp, (minDisparity - 1) * 16, speckleWindowSize, 16 * speckleRange).
+ * disparity: image b at disparity + b*image_stride, rows `pitch` apart (both in int16 elements;
+ *            pitch >= width, e.g. a column range of a wider map).  height*width <= INT32_MAX.
+ * workspace: device scratch of fvo_speckle_workspace_bytes(batch, height, width) bytes (8 per
+ *            pixel; caller-owned, 4-byte aligned, needs no clearing between calls); that function
+ *            returns -1 for sizes the filter refuses.
+ * Arguments are checked even when nothing is launched: batch == 0 (checked like every entry
+ * point: before the pointers) and max_speckle_size <= 0 (nothing is a speckle) return 0. */
+int64_t fvo_speckle_workspace_bytes(int32_t batch, int32_t height, int32_t width);
+int fvo_filter_speckles(fvo_ctx* ctx, int16_t* disparity, int32_t batch, int32_t height, int32_t width,
+                        int64_t image_stride, int32_t pitch, int32_t new_val, int32_t max_speckle_size,
+                        int32_t max_diff, void* workspace, int64_t workspace_bytes, fvo_stream stream);
 
 /* Test hook: KeyPointsFilter::retainBest on `n` float responses (device memory) with the
  * product's selection kernel.  idx_out [n] receives the surviving original indices in
