@@ -4,11 +4,14 @@
 // The specification — landmark construction, residuals, robust weights, LM schedule —
 // is oracle/ba_ref.py; this file implements it in fp64.
 //
-// Problem construction, one block per window:
+// Problem construction:
 //   k_ba_stereo  per keypoint, the reference's float32 back-projection through the
 //                disparity map (the fvo_backproject arithmetic) -> (X, Y, Z, d)
-//   k_ba_build   match-chain landmarks (ordered births via block scans), landmark-major
-//                observations, per-frame observation lists, initial poses / LM state
+//   k_ba_births  (window, birth frame): the frame's match-chain landmark and observation counts
+//   k_ba_emit    (window, birth frame): ids from the prefix over the counts, the landmarks and
+//                their landmark-major observations
+//   k_ba_lists   (window, frame): per-frame observation lists, initial poses / LM state
+//   (k_ba_maps   (window, frame) first, when the forward match maps do not fit in LDS)
 // One LM iteration = five launches whose grids span every window x chunk, so the whole
 // GPU works on the batch of windows (one block per window would leave most CUs idle and
 // every phase latency-bound):
@@ -230,6 +233,23 @@ __device__ __forceinline__ void mat_mul_T(const double* A, const double* B, doub
   }
 }
 
+// the initial poses of a window starting at frame s: T_0 = I, T_{k+1} = rel_{s+k} T_k.  T becomes
+// T_last; the poses T_0 .. T_last are also stored to out[] unless it is null
+__device__ __forceinline__ void pose_chain(const double* Trel, int s, int last, double* T, double (*out)[12]) {
+  double U[12];
+  for (int i = 0; i < 12; ++i) T[i] = (i < 9 && i % 4 == 0) ? 1.0 : 0.0;
+  for (int k = 0; k <= last; ++k) {
+    if (out)
+      for (int i = 0; i < 12; ++i) out[k][i] = T[i];
+    if (k < last) {
+      const double* M = Trel + (int64_t)(s + k) * 16;
+      const double A[12] = {M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10], M[3], M[7], M[11]};
+      mat_mul_T(A, T, U);
+      for (int i = 0; i < 12; ++i) T[i] = U[i];
+    }
+  }
+}
+
 __device__ __forceinline__ void exp_so3(const double* w, double* R) {
   const double th = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
   if (th < 1e-12) {
@@ -366,232 +386,25 @@ __device__ __forceinline__ bool ba_outlier(const double* T, const double* X, con
 }
 
 // ------------------------------------------------------------------ problem construction
-// k_ba_build: one 512-thread block per window, birth frames in order.  Since r4 it runs only
-// when the window's u16 match maps do not fit in LDS (LMAP = false: the maps in the global
-// v.next copy); otherwise k_ba_births / k_ba_emit / k_ba_lists build the same problem on a
-// (window, frame) grid (below; 1080p 0.55 ms -> BA 5.0 -> 4.63 ms, 600p 1.86 -> 1.81 ms,
-// bit-identical results).  Following a track -- a chain of dependent lookups up to K-1 long --
-// costs LDS latency with the maps in LDS; each candidate records its chain in registers on
-// the first walk, and the keypoints along it are then loaded all at once.
-constexpr int kBuildBlock = 512;
-template <bool LMAP>
-__global__ __launch_bounds__(kBuildBlock) void k_ba_build(BaIn in, void* ws, BaDims dm, int first_end, int first_valid) {
-  extern __shared__ uint8_t s_dyn[];  // LMAP: [K-1][cap] u16 maps, then [cap] tracked flags
-  __shared__ double sT[kKMax][12];
-  __shared__ int s_tmp[kBuildBlock / 64];
-  __shared__ int s_L, s_O, s_stop;
-  const int w = blockIdx.x, tid = threadIdx.x;
-  const int e = first_end + w;
-  const int s = max(first_valid, e - dm.K + 1);
-  const int n = e - s + 1;
-  BaWin v = view(ws, dm, w);
-  BaState* S = v.st;
-  const int cap = dm.cap;
-  uint16_t* s_next = reinterpret_cast<uint16_t*>(s_dyn);
-  uint8_t* s_tracked = LMAP ? s_dyn + 2 * (dm.K - 1) * cap : s_dyn;
-  auto nxt = [&](int k, int b) -> int {
-    if (LMAP) {
-      const int r = s_next[k * cap + b];
-      return r == 0xFFFF ? -1 : r;
-    }
-    return v.next[k * cap + b];
-  };
-  if (tid == 0) {
-    S->L = 0;
-    S->O = 0;
-    S->n = n;
-    S->s = s;
-    S->active = 0;
-    s_L = 0;
-    s_O = 0;
-    s_stop = 0;
-  }
-  if (n < 3) return;
-  if (tid == 0) {  // initial poses: T_0 = I, T_{k+1} = rel_{s+k} T_k
-    for (int i = 0; i < 12; ++i) sT[0][i] = (i < 9 && i % 4 == 0) ? 1.0 : 0.0;
-    for (int k = 0; k + 1 < n; ++k) {
-      const double* M = in.Trel + (int64_t)(s + k) * 16;
-      const double A[12] = {M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10], M[3], M[7], M[11]};
-      mat_mul_T(A, sT[k], sT[k + 1]);
-    }
-  }
-  // forward match maps of frames s..e-1
-  for (int k = 0; k + 1 < n; ++k)
-    for (int i = tid; i < cap; i += kBuildBlock) {
-      if (LMAP) s_next[k * cap + i] = 0xFFFF;
-      else v.next[k * cap + i] = -1;
-    }
-  __syncthreads();
-  for (int k = 0; k + 1 < n; ++k) {
-    const int f = s + k, M = min(max(in.nmatch[f], 0), cap);
-    const int32_t* m = in.matches + (int64_t)f * cap * 3;
-    for (int r = tid; r < M; r += kBuildBlock) {
-      if (LMAP) s_next[k * cap + m[3 * r]] = (uint16_t)m[3 * r + 1];
-      else v.next[k * cap + m[3 * r]] = m[3 * r + 1];
-    }
-  }
-  __syncthreads();
-  for (int j = 0; j + 1 < n; ++j) {
-    const int f = s + j;
-    for (int i = tid; i < cap; i += kBuildBlock) s_tracked[i] = 0;
-    __syncthreads();
-    if (j > 0) {
-      const int Mp = min(max(in.nmatch[f - 1], 0), cap);
-      const int32_t* mp = in.matches + (int64_t)(f - 1) * cap * 3;
-      for (int r = tid; r < Mp; r += kBuildBlock) s_tracked[mp[3 * r + 1]] = 1;
-    }
-    __syncthreads();
-    const int M = min(max(in.nmatch[f], 0), cap);
-    const int32_t* m = in.matches + (int64_t)f * cap * 3;
-    const double* Tj = sT[j];
-    for (int base = 0; base < M; base += kBuildBlock) {
-      if (s_stop) break;  // uniform: written before the last barrier
-      const int r = base + tid;
-      bool cand = false;
-      int len = 0, q = 0;
-      int bs[kKMax - 1];  // the track's keypoint in frames j+1, j+2, ... (static indices only)
-      float4 sp = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (r < M) {
-        q = m[3 * r];
-        bs[0] = m[3 * r + 1];
-        sp = in.stereo[(int64_t)f * cap + q];
-        cand = !s_tracked[q] && sp.z > 0.f;
-      }
-      if (cand) {
-        len = 2;
-        bool go = true;
-#pragma unroll
-        for (int kk = 1; kk < kKMax - 1; ++kk) {  // frame j + kk + 1 from frame j + kk
-          const int k = j + kk;
-          if (go && k + 1 < n) {
-            const int nb = nxt(k, bs[kk - 1]);
-            if (nb < 0) go = false;
-            else { bs[kk] = nb; ++len; }
-          } else {
-            go = false;
-          }
-        }
-      }
-      // one scan of (observations << 10 | candidate): len <= 21, so both sums fit
-      int tp;
-      const int packed = block_scan_n<kBuildBlock>((len << 10) | (cand ? 1 : 0), s_tmp, &tp);
-      const int lid = packed & 1023, oof = packed >> 10, tl = tp & 1023, to = tp >> 10;
-      const int L0 = s_L, O0 = s_O;
-      // creation stops at the first landmark that does not fit (the failing rows are a
-      // suffix of this chunk's candidates: both prefix sums are monotone); when the whole
-      // chunk fits (the block totals say so, uniformly) no per-thread test is needed
-      const bool allfit = L0 + tl <= dm.Lmax && O0 + to <= dm.Omax;
-      const bool ok = cand && (allfit || ((L0 + lid < dm.Lmax) && (O0 + oof + len <= dm.Omax)));
-      const int nok = allfit ? tl : __syncthreads_count(ok);
-      const int nfail = allfit ? 0 : __syncthreads_count(cand && !ok);
-      if (ok) {
-        const int id = L0 + lid;
-        int o = O0 + oof;
-        // X_world = R^T (Xc - t)
-        const double Xc[3] = {(double)sp.x - Tj[9], (double)sp.y - Tj[10], (double)sp.z - Tj[11]};
-        for (int i = 0; i < 3; ++i) v.X0[3 * id + i] = Tj[i] * Xc[0] + Tj[3 + i] * Xc[1] + Tj[6 + i] * Xc[2];
-        v.lstart[id] = o;
-        const float* kq = in.kp + ((int64_t)f * cap + q) * FVO_KP_STRIDE;
-        const int oq = min(max((int)kq[5], 0), in.nlev - 1);
-        v.obs[o++] = BaObs{id, (short)j, (short)oq, kq[0], kq[1], kq[0] - sp.w};
-        // the track's keypoints: every load issued before the first observation is written
-        float ku[kKMax - 1], kvv[kKMax - 1], ko[kKMax - 1];
-#pragma unroll
-        for (int kk = 0; kk < kKMax - 1; ++kk)
-          if (kk < len - 1) {
-            const float* kb = in.kp + ((int64_t)(s + j + 1 + kk) * cap + bs[kk]) * FVO_KP_STRIDE;
-            ku[kk] = kb[0];
-            kvv[kk] = kb[1];
-            ko[kk] = kb[5];
-          }
-#pragma unroll
-        for (int kk = 0; kk < kKMax - 1; ++kk)
-          if (kk < len - 1) {
-            const int ob = min(max((int)ko[kk], 0), in.nlev - 1);
-            v.obs[o++] = BaObs{id, (short)(j + 1 + kk), (short)ob, ku[kk], kvv[kk], __builtin_nanf("")};
-          }
-      }
-      int tot_ok = to;
-      if (!allfit) (void)block_scan_n<kBuildBlock>(ok ? len : 0, s_tmp, &tot_ok);
-      if (tid == 0) {
-        s_L = L0 + nok;
-        s_O = O0 + tot_ok;
-        if (nfail) s_stop = 1;
-      }
-      __syncthreads();
-    }
-    __syncthreads();
-    if (s_stop) break;
-  }
-  __syncthreads();
-  const int L = s_L, O = s_O;
-  // per-frame observation lists (stable, landmark-major order inside a frame): a counting
-  // sort -- frame sizes by LDS atomics, then per 512-observation chunk every wave ranks its
-  // lanes within each frame by ballots, the waves' counts give the chunk's offsets (three
-  // barriers per chunk instead of two per frame per chunk)
-  __shared__ int s_fcnt[kKMax], s_foff[kKMax], s_wcnt[kBuildBlock / 64][kKMax];
-  if (tid < kKMax) s_fcnt[tid] = 0;
-  __syncthreads();
-  for (int i = tid; i < O; i += kBuildBlock) atomicAdd(&s_fcnt[v.obs[i].frame], 1);
-  __syncthreads();
-  if (tid == 0) {
-    int acc = 0;
-    for (int f = 0; f < n; ++f) {
-      v.hdr[8 + f] = acc;
-      s_foff[f] = acc;
-      acc += s_fcnt[f];
-    }
-    v.hdr[8 + n] = acc;
-  }
-  __syncthreads();
-  const int lane = tid & 63, wid = tid >> 6;
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  for (int base = 0; base < O; base += kBuildBlock) {
-    const int i = base + tid;
-    const int f = i < O ? (int)v.obs[i].frame : -1;
-    int rank = 0;
-    for (int ff = 0; ff < n; ++ff) {
-      const unsigned long long mk = __ballot(f == ff);
-      if (f == ff) rank = __popcll(mk & lt);
-      if (lane == 0) s_wcnt[wid][ff] = __popcll(mk);
-    }
-    __syncthreads();
-    if (f >= 0) {
-      int pos = s_foff[f] + rank;
-      for (int w2 = 0; w2 < wid; ++w2) pos += s_wcnt[w2][f];
-      v.flist[pos] = i;
-    }
-    __syncthreads();
-    if (tid < n) {
-      int c = 0;
-      for (int w2 = 0; w2 < kBuildBlock / 64; ++w2) c += s_wcnt[w2][tid];
-      s_foff[tid] += c;
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    v.lstart[L] = O;
-    S->L = L;
-    S->O = O;
-    S->active = L > 0;
-    S->lam = kLam0;
-    S->parity = 0;
-    S->fail = 0;
-    S->acc = 0;
-    S->cost = 0.0;
-    S->cost0 = 0.0;
-  }
-  for (int i = tid; i < n * 12; i += kBuildBlock) S->T[i / 12][i % 12] = sT[i / 12][i % 12];
-}
-
-// ---- parallel construction (r4): the same landmarks, ids, observations and per-frame lists
-// as k_ba_build<true>, from a (window, frame) grid instead of one block per window.  A
-// landmark is born at frame j from j's match rows alone (the tracked test reads frame j-1's
-// matches, the track follows the maps of frames j+1..), so every birth frame is counted and
-// emitted by its own block; the ids come from prefix sums over the birth frames, and the
-// lists per observed frame from a scan over the landmarks.  Creation stops at the first
-// candidate in (frame, row) order that does not fit: both prefix sums are monotone, so a
-// candidate is created iff its all-candidate prefixes fit -- the same set as the serial stop.
+// The landmarks, ids, observations and per-frame lists of oracle/ba_ref.py build_problem, from a
+// (window, frame) grid (r4; a serial construction, one block per window, gave the same bits:
+// 1080p 0.55 ms -> BA 5.0 -> 4.63 ms, 600p 1.86 -> 1.81 ms).  A landmark is born at frame j
+// from j's match rows alone (the tracked test reads frame j-1's matches, the track follows the
+// maps of frames j+1..), so every birth frame is counted and emitted by its own block; the ids
+// come from prefix sums over the birth frames, and the lists per observed frame from a scan
+// over the landmarks.  Creation stops at the first candidate in (frame, row) order that does
+// not fit: both prefix sums are monotone, so a candidate is created iff its all-candidate
+// prefixes fit -- the same set as stopping in order.  Following a track is a chain of dependent
+// lookups up to K-1 long; each candidate records its chain in registers on the walk, and the
+// keypoints along it are then loaded all at once.
+// The forward match maps (keypoint of frame k -> its match in frame k+1) live in one of two
+// places, chosen by build_shm(); everything else is the same code:
+//   GMAP = false  u16 in the block's dynamic LDS, 0xFFFF = no match; each block builds the maps
+//                 its walks read (every benchmarked shape)
+//   GMAP = true   int32 in the window's workspace v.next, -1 = no match, built once per window
+//                 by k_ba_maps ahead of k_ba_births (maps that do not fit in LDS, or cap >=
+//                 65535 where an index would collide with the u16 sentinel)
+// The tracked flags [cap] are in dynamic LDS in both.
 // r6: 512 threads (half the row passes over a birth frame's matches in k_ba_emit; bit-identical):
 // 1080p BA 3.24 -> 3.17-3.19 ms; 600p BA and overlapped bench within noise (two A/Bs: +0.8 %, -0.3 %)
 constexpr int kBirthBlock = 512;
@@ -612,19 +425,54 @@ __device__ __forceinline__ BirthFrame birth_frame(const BaIn& in, const BaDims& 
   return b;
 }
 
-// the u16 forward maps of frames j+1 .. n-2 and frame j's tracked flags (from frame j-1's rows)
-__device__ void birth_maps(const BaIn& in, const BaDims& dm, const BirthFrame& b, int j, uint16_t* s_next,
-                           uint8_t* s_tr) {
+// where the forward maps live (above): element type, "no match" value, and the block's pointers
+template <bool GMAP>
+using birth_map_t = std::conditional_t<GMAP, int32_t, uint16_t>;
+template <bool GMAP>
+constexpr int kNoMatch = GMAP ? -1 : 0xFFFF;
+template <bool GMAP>
+__device__ __forceinline__ const birth_map_t<GMAP>* birth_map_ptr(const BaWin& v, uint8_t* s_dyn) {
+  if constexpr (GMAP) return v.next;
+  else return reinterpret_cast<const uint16_t*>(s_dyn);
+}
+template <bool GMAP>
+__device__ __forceinline__ uint8_t* birth_flags_ptr(const BaDims& dm, uint8_t* s_dyn) {
+  return GMAP ? s_dyn : s_dyn + 2 * (dm.K - 1) * dm.cap;
+}
+
+// GMAP: map k of a window (1 <= k <= n-2, the ones a track walk reads) by block (w, k - 1): the
+// fill, then the frame's match rows.  Not left to the (window, birth frame) blocks, which would
+// write maps other blocks read.
+__global__ __launch_bounds__(kBirthBlock) void k_ba_maps(BaIn in, void* ws, BaDims dm, int first_end,
+                                                         int first_valid) {
+  const int w = blockIdx.x, k = blockIdx.y + 1, tid = threadIdx.x, cap = dm.cap;
+  const int e = first_end + w, s = max(first_valid, e - dm.K + 1), n = e - s + 1;
+  if (n < 3 || k + 1 >= n) return;
+  int* next = view(ws, dm, w).next + (int64_t)k * cap;
+  for (int i = tid; i < cap; i += kBirthBlock) next[i] = -1;
+  __syncthreads();
+  const int f = s + k, M = min(max(in.nmatch[f], 0), cap);
+  const int32_t* m = in.matches + (int64_t)f * cap * 3;
+  for (int r = tid; r < M; r += kBirthBlock) next[m[3 * r]] = m[3 * r + 1];
+}
+
+// frame j's tracked flags (from frame j-1's rows) and, in LDS, the maps of frames j+1 .. n-2
+template <bool GMAP>
+__device__ void birth_maps(const BaIn& in, const BaDims& dm, const BirthFrame& b, int j, uint8_t* s_dyn) {
   const int cap = dm.cap, tid = threadIdx.x;
-  for (int k = j + 1; k + 1 < b.n; ++k)
-    for (int i = tid; i < cap; i += kBirthBlock) s_next[k * cap + i] = 0xFFFF;
+  uint16_t* s_next = reinterpret_cast<uint16_t*>(s_dyn);
+  uint8_t* s_tr = birth_flags_ptr<GMAP>(dm, s_dyn);
+  if constexpr (!GMAP)
+    for (int k = j + 1; k + 1 < b.n; ++k)
+      for (int i = tid; i < cap; i += kBirthBlock) s_next[k * cap + i] = 0xFFFF;
   for (int i = tid; i < cap; i += kBirthBlock) s_tr[i] = 0;
   __syncthreads();
-  for (int k = j + 1; k + 1 < b.n; ++k) {
-    const int f = b.s + k, M = min(max(in.nmatch[f], 0), cap);
-    const int32_t* m = in.matches + (int64_t)f * cap * 3;
-    for (int r = tid; r < M; r += kBirthBlock) s_next[k * cap + m[3 * r]] = (uint16_t)m[3 * r + 1];
-  }
+  if constexpr (!GMAP)
+    for (int k = j + 1; k + 1 < b.n; ++k) {
+      const int f = b.s + k, M = min(max(in.nmatch[f], 0), cap);
+      const int32_t* m = in.matches + (int64_t)f * cap * 3;
+      for (int r = tid; r < M; r += kBirthBlock) s_next[k * cap + m[3 * r]] = (uint16_t)m[3 * r + 1];
+    }
   if (j > 0) {
     const int Mp = min(max(in.nmatch[b.f - 1], 0), cap);
     const int32_t* mp = in.matches + (int64_t)(b.f - 1) * cap * 3;
@@ -634,8 +482,9 @@ __device__ void birth_maps(const BaIn& in, const BaDims& dm, const BirthFrame& b
 }
 
 // row r of frame j: candidate test and track (len observations, keypoints bs[] in j+1, ...)
+template <bool GMAP>
 __device__ __forceinline__ bool birth_track(const BaIn& in, const BaDims& dm, const BirthFrame& b, int j, int r,
-                                            const uint16_t* s_next, const uint8_t* s_tr, int& len, int& q,
+                                            const birth_map_t<GMAP>* next, const uint8_t* s_tr, int& len, int& q,
                                             int (&bs)[kKMax - 1], float4& sp) {
   len = 0;
   q = 0;
@@ -651,8 +500,8 @@ __device__ __forceinline__ bool birth_track(const BaIn& in, const BaDims& dm, co
   for (int kk = 1; kk < kKMax - 1; ++kk) {
     const int k = j + kk;
     if (go && k + 1 < b.n) {
-      const int nb = s_next[k * dm.cap + bs[kk - 1]];
-      if (nb == 0xFFFF) go = false;
+      const int nb = next[k * dm.cap + bs[kk - 1]];
+      if (nb == kNoMatch<GMAP>) go = false;
       else { bs[kk] = nb; ++len; }
     } else {
       go = false;
@@ -673,9 +522,10 @@ __device__ __forceinline__ int block_isum(int v, int* s_tmp) {  // all threads g
 }
 
 // (window, birth frame): candidate and observation counts of the frame's rows
+template <bool GMAP>
 __global__ __launch_bounds__(kBirthBlock) void k_ba_births(BaIn in, void* ws, BaDims dm, int first_end,
                                                            int first_valid) {
-  extern __shared__ uint8_t s_dyn[];  // [K-1][cap] u16 maps, then [cap] tracked flags
+  extern __shared__ uint8_t s_dyn[];  // ([K-1][cap] u16 maps unless GMAP, then) [cap] tracked flags
   __shared__ int s_tmp[kBirthBlock / 64];
   const int w = blockIdx.x, j = blockIdx.y;
   BaWin v = view(ws, dm, w);
@@ -685,14 +535,14 @@ __global__ __launch_bounds__(kBirthBlock) void k_ba_births(BaIn in, void* ws, Ba
     if (threadIdx.x == 0) { v.bld[kBldL + j] = 0; v.bld[kBldO + j] = 0; }
     return;
   }
-  uint16_t* s_next = reinterpret_cast<uint16_t*>(s_dyn);
-  uint8_t* s_tr = s_dyn + 2 * (dm.K - 1) * dm.cap;
-  birth_maps(in, dm, b, j, s_next, s_tr);
+  const birth_map_t<GMAP>* next = birth_map_ptr<GMAP>(v, s_dyn);
+  const uint8_t* s_tr = birth_flags_ptr<GMAP>(dm, s_dyn);
+  birth_maps<GMAP>(in, dm, b, j, s_dyn);
   int nl = 0, no = 0;
   for (int r = threadIdx.x; r < b.M; r += kBirthBlock) {
     int len, q, bs[kKMax - 1];
     float4 sp;
-    if (birth_track(in, dm, b, j, r, s_next, s_tr, len, q, bs, sp)) { ++nl; no += len; }
+    if (birth_track<GMAP>(in, dm, b, j, r, next, s_tr, len, q, bs, sp)) { ++nl; no += len; }
   }
   nl = block_isum(nl, s_tmp);
   no = block_isum(no, s_tmp);
@@ -700,7 +550,8 @@ __global__ __launch_bounds__(kBirthBlock) void k_ba_births(BaIn in, void* ws, Ba
 }
 
 // (window, birth frame): ids from the prefix over earlier birth frames, then the landmarks and
-// their observations exactly as k_ba_build writes them
+// their observations
+template <bool GMAP>
 __global__ __launch_bounds__(kBirthBlock) void k_ba_emit(BaIn in, void* ws, BaDims dm, int first_end,
                                                          int first_valid) {
   extern __shared__ uint8_t s_dyn[];
@@ -718,26 +569,20 @@ __global__ __launch_bounds__(kBirthBlock) void k_ba_emit(BaIn in, void* ws, BaDi
   }
   if (L0 >= dm.Lmax || O0 >= dm.Omax) return;  // every candidate of this frame fails
   if (tid < kKMax) s_fc[tid] = 0;
-  if (tid == 0) {  // the pose of frame j: T_0 = I, T_{k+1} = rel_{s+k} T_k (k_ba_build's chain)
-    double T[12], U[12];
-    for (int i = 0; i < 12; ++i) T[i] = (i < 9 && i % 4 == 0) ? 1.0 : 0.0;
-    for (int k = 0; k < j; ++k) {
-      const double* M = in.Trel + (int64_t)(b.s + k) * 16;
-      const double A[12] = {M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10], M[3], M[7], M[11]};
-      mat_mul_T(A, T, U);
-      for (int i = 0; i < 12; ++i) T[i] = U[i];
-    }
+  if (tid == 0) {  // the pose of frame j
+    double T[12];
+    pose_chain(in.Trel, b.s, j, T, nullptr);
     for (int i = 0; i < 12; ++i) sTj[i] = T[i];
   }
-  uint16_t* s_next = reinterpret_cast<uint16_t*>(s_dyn);
-  uint8_t* s_tr = s_dyn + 2 * (dm.K - 1) * dm.cap;
-  birth_maps(in, dm, b, j, s_next, s_tr);  // (barriers: sTj / s_fc visible after it)
+  const birth_map_t<GMAP>* next = birth_map_ptr<GMAP>(v, s_dyn);
+  const uint8_t* s_tr = birth_flags_ptr<GMAP>(dm, s_dyn);
+  birth_maps<GMAP>(in, dm, b, j, s_dyn);  // (barriers: sTj / s_fc visible after it)
   int okl = 0, oko = 0;
   for (int base = 0; base < b.M; base += kBirthBlock) {
     const int r = base + tid;
     int len, q, bs[kKMax - 1];
     float4 sp;
-    const bool cand = birth_track(in, dm, b, j, r, s_next, s_tr, len, q, bs, sp);
+    const bool cand = birth_track<GMAP>(in, dm, b, j, r, next, s_tr, len, q, bs, sp);
     int tp;
     const int packed = block_scan_n<kBirthBlock>((len << 10) | (cand ? 1 : 0), s_tmp, &tp);
     const int lid = packed & 1023, oof = packed >> 10;
@@ -814,17 +659,8 @@ __global__ __launch_bounds__(kBirthBlock) void k_ba_lists(BaIn in, void* ws, BaD
         acc += v.bld[kBldF + f];
       }
       v.hdr[8 + n] = acc;
-      double T[12], U[12];
-      for (int i = 0; i < 12; ++i) T[i] = (i < 9 && i % 4 == 0) ? 1.0 : 0.0;
-      for (int f = 0; f < n; ++f) {
-        for (int i = 0; i < 12; ++i) S->T[f][i] = T[i];
-        if (f + 1 < n) {
-          const double* M = in.Trel + (int64_t)(s + f) * 16;
-          const double A[12] = {M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10], M[3], M[7], M[11]};
-          mat_mul_T(A, T, U);
-          for (int i = 0; i < 12; ++i) T[i] = U[i];
-        }
-      }
+      double T[12];
+      pose_chain(in.Trel, s, n - 1, T, S->T);
     }
   }
   if (!live || k >= n || L == 0) return;
@@ -1292,7 +1128,9 @@ __global__ __launch_bounds__(kSolveBlock) void k_ba_solve(void* ws, BaDims dm) {
   // iteration, ~0.8 ms of the 1080p BA by a no-assembly ablation)
   typedef double d4 __attribute__((ext_vector_type(4)));
   const int nq = (np + 3) / 4;  // column quads per row
-  constexpr int kAsmIt = 8;     // ceil(np nq / kSolveBlock) <= 7 for np <= 120
+  constexpr int kAsmIt = 8;     // ceil(np nq / kSolveBlock): exactly 8 at np = 120 (3600 / 512)
+  static_assert(kAsmIt * kSolveBlock >= 6 * (kKMax - 1) * ((6 * (kKMax - 1) + 3) / 4),
+                "every (row, column quad) of the largest reduced system is assembled");
   d4 gq[kAsmIt];
   double hq[kAsmIt][4];
 #pragma unroll
@@ -1744,11 +1582,24 @@ BaDims make_dims(const fvo_ctx* ctx) {
   return d;
 }
 
-// k_ba_build's dynamic LDS: the u16 match maps + tracked flags when they fit (and cap < 65535),
-// else the flags alone (maps in the global workspace)
+// dynamic LDS of k_ba_births / k_ba_emit: the u16 match maps + tracked flags when they fit (and
+// cap < 65535), else the flags alone (GMAP: the maps in the global workspace)
 size_t build_shm(const BaDims& d) {
   const size_t maps = (size_t)2 * (d.K - 1) * d.cap + d.cap;
   return (d.cap < 0xFFFF && maps <= 156 * 1024) ? maps : (size_t)d.cap;  // + ~4 KB static <= 160 KiB
+}
+bool build_gmap(const BaDims& d) { return build_shm(d) == (size_t)d.cap; }
+
+// the counting step of the construction (fvo_ba_count_births may run it ahead of fvo_ba_windows)
+void ba_births_launch(const BaIn& in, void* ws, const BaDims& d, int nw, int fe, int first_valid, hipStream_t s) {
+  const dim3 g(nw, d.K - 1), blk(kBirthBlock);
+  const size_t shb = build_shm(d);
+  if (build_gmap(d)) {
+    hipLaunchKernelGGL(k_ba_maps, dim3(nw, d.K - 2), blk, 0, s, in, ws, d, fe, first_valid);
+    hipLaunchKernelGGL(k_ba_births<true>, g, blk, shb, s, in, ws, d, fe, first_valid);
+  } else {
+    hipLaunchKernelGGL(k_ba_births<false>, g, blk, shb, s, in, ws, d, fe, first_valid);
+  }
 }
 size_t lin_shm(const BaDims& d) { return (size_t)8 * 3 * d.LPC * (d.NR + 2); }
 size_t solve_shm(int K) {
@@ -1773,10 +1624,11 @@ int ba_init(fvo_ctx* ctx) {
   FVO_HIP(ctx, hipEventCreateWithFlags(&ctx->ba_join, hipEventDisableTiming));
   // dynamic LDS above 64 KiB: the MFMA slice always, the reduced system for K > 11, the match maps
   if (build_shm(d) > 65536) {
-    FVO_HIP(ctx, hipFuncSetAttribute((const void*)k_ba_births, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)build_shm(d)));
-    FVO_HIP(ctx, hipFuncSetAttribute((const void*)k_ba_emit, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)build_shm(d)));
+    const bool g = build_gmap(d);
+    FVO_HIP(ctx, hipFuncSetAttribute(g ? (const void*)k_ba_births<true> : (const void*)k_ba_births<false>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)build_shm(d)));
+    FVO_HIP(ctx, hipFuncSetAttribute(g ? (const void*)k_ba_emit<true> : (const void*)k_ba_emit<false>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)build_shm(d)));
   }
   FVO_HIP(ctx, hipFuncSetAttribute((const void*)k_ba_lin<kLinTiles64>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)lin_shm(d)));
@@ -1806,14 +1658,12 @@ void ba_windows_launch(fvo_ctx* ctx, const BaIn& in, const BaCam& cam, const BaD
   void* ws = static_cast<char*>(ctx->ba_ws) + (int64_t)d.win * w0;
   const int fe = first_end + w0;
   const size_t shb = build_shm(d);
-  if (shb > (size_t)d.cap) {  // the match maps fit in LDS: the parallel construction
-    if (!births_done)  // (fvo_ba_count_births ran it ahead for this window range)
-      hipLaunchKernelGGL(k_ba_births, dim3(nw, d.K - 1), dim3(kBirthBlock), shb, s, in, ws, d, fe, first_valid);
-    hipLaunchKernelGGL(k_ba_emit, dim3(nw, d.K - 1), dim3(kBirthBlock), shb, s, in, ws, d, fe, first_valid);
-    hipLaunchKernelGGL(k_ba_lists, dim3(nw, d.K), dim3(kBirthBlock), 0, s, in, ws, d, fe, first_valid);
-  } else {
-    hipLaunchKernelGGL(k_ba_build<false>, dim3(nw), dim3(kBuildBlock), shb, s, in, ws, d, fe, first_valid);
-  }
+  if (!births_done) ba_births_launch(in, ws, d, nw, fe, first_valid, s);  // (else fvo_ba_count_births ran it ahead)
+  if (build_gmap(d))
+    hipLaunchKernelGGL(k_ba_emit<true>, dim3(nw, d.K - 1), dim3(kBirthBlock), shb, s, in, ws, d, fe, first_valid);
+  else
+    hipLaunchKernelGGL(k_ba_emit<false>, dim3(nw, d.K - 1), dim3(kBirthBlock), shb, s, in, ws, d, fe, first_valid);
+  hipLaunchKernelGGL(k_ba_lists, dim3(nw, d.K), dim3(kBirthBlock), 0, s, in, ws, d, fe, first_valid);
   const dim3 gcu(nw, d.NCU), gch(nw, d.NPART), gfr(nw, d.K - 1);
   const size_t shl = lin_shm(d), shs = solve_shm(d.K);
   hipLaunchKernelGGL(k_ba_cost, gcu, dim3(kBlock), 0, s, in, ws, d, cam, 0);
@@ -1854,8 +1704,9 @@ int ba_run(fvo_ctx* ctx, const float* kp, const int32_t* nkp, const int32_t* mat
   const BaCam cam{K[0], K[4], K[2], K[5], baseline};
   // the birth counts of exactly this call's window range already computed (fvo_ba_count_births)?
   const auto& pb = ctx->ba_births;
-  const bool births_done = pb.valid && pb.matches == matches && pb.stereo == stereo && pb.nframes == nframes &&
-                           pb.first_end == first_end && pb.nwin == nwin && pb.first_valid == first_valid;
+  const bool births_done = pb.valid && pb.matches == matches && pb.nmatch == nmatch && pb.stereo == stereo &&
+                           pb.nframes == nframes && pb.first_end == first_end && pb.nwin == nwin &&
+                           pb.first_valid == first_valid;
   ctx->ba_births.valid = false;
   // The windows are independent: the batch is split in two halves whose LM sequences run on
   // two streams, so one half's latency-bound kernels (build, the per-window solve on one
@@ -1880,8 +1731,8 @@ int ba_run(fvo_ctx* ctx, const float* kp, const int32_t* nkp, const int32_t* mat
   return 0;
 }
 
-// k_ba_births of every window of a coming fvo_ba_windows call, ahead of it (it reads the match rows
-// and the stereo points only); recorded so that call skips it
+// the counting step of every window of a coming fvo_ba_windows call, ahead of it (it reads the match
+// rows and the stereo points only); recorded so that call skips it
 int ba_births_run(fvo_ctx* ctx, const int32_t* matches, const int32_t* nmatch, const float* stereo, int nframes,
                   int cap, int first_end, int nwin, int first_valid, hipStream_t s) {
   if (cap != ctx->kp_cap) return fvo_fail(ctx, "ba: cap must equal the context keypoint capacity");
@@ -1889,15 +1740,13 @@ int ba_births_run(fvo_ctx* ctx, const int32_t* matches, const int32_t* nmatch, c
   if (first_end < 1 || first_end + nwin > nframes) return fvo_fail(ctx, "ba: windows exceed the frame range");
   if (first_valid < 0 || first_valid >= first_end) return fvo_fail(ctx, "ba: first_valid out of range");
   const BaDims d = make_dims(ctx);
-  const size_t shb = build_shm(d);
-  if (!(shb > (size_t)d.cap)) return 0;  // serial construction: fvo_ba_windows counts in k_ba_build
   BaIn in{nullptr, nullptr, matches, nmatch, reinterpret_cast<const float4*>(stereo), nullptr, {}, 1};
-  hipLaunchKernelGGL(k_ba_births, dim3(nwin, d.K - 1), dim3(kBirthBlock), shb, s, in, ctx->ba_ws, d, first_end,
-                     first_valid);
+  ba_births_launch(in, ctx->ba_ws, d, nwin, first_end, first_valid, s);
   FVO_LAUNCH_CHECK(ctx);
   auto& pb = ctx->ba_births;
   pb.valid = true;
   pb.matches = matches;
+  pb.nmatch = nmatch;
   pb.stereo = stereo;
   pb.nframes = nframes;
   pb.first_end = first_end;

@@ -89,6 +89,7 @@ struct fvo_ctx {
   struct {
     bool valid = false;
     const void* matches = nullptr;
+    const void* nmatch = nullptr;
     const void* stereo = nullptr;
     int nframes = 0, first_end = 0, nwin = 0, first_valid = 0;
   } ba_births;

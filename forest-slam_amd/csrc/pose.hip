@@ -1485,7 +1485,7 @@ __global__ __launch_bounds__(64) void k_pnp_hyp_a(int maxIters, int batch, const
 // (hyp_b at 276 registers: 2.6-3.4 ms per launch beside k_sg_rows).  Measured (bench.py, 20
 // steps, 2 runs each): unbounded 5110 frames/s; hyp_b at 256 / 168 / 128 VGPRs 5130 / 5177 /
 // 5173; then refine at 256 / 168 VGPRs 5237 / 5222 (in-order PnP 1.57 -> 1.73 ms).  Forcing
-// k_ba_build (512 threads) to 128 VGPRs instead collapsed the overlapped step (21 ms).
+// the BA's then serial construction kernel (512 threads) to 128 VGPRs instead collapsed the overlapped step (21 ms).
 __global__ __launch_bounds__(64, 3) void k_pnp_hyp_b(const float* __restrict__ P3all, const float* __restrict__ p2all,
                                                   int cap, Cam K, float thr2, int maxIters, int batch,
                                                   const int32_t* __restrict__ plan,

@@ -220,11 +220,11 @@ int fvo_ba_windows(fvo_ctx* ctx, const float* keypoints, const int32_t* n_keypoi
 /* The first step of fvo_ba_windows -- counting each window's landmark births and observations
  * per birth frame -- issued ahead of it, e.g. on a side stream while PnP runs (it reads only the
  * match rows and the keypoints' stereo points, not T_rel or the keypoints).  Arguments as for
- * fvo_ba_windows.  The next fvo_ba_windows call on this context with the same matches, stereo,
- * n_frames, first_end, n_windows and first_valid skips that step; the caller orders the two calls
- * (the stream of fvo_ba_windows waits for this one's).  Any other BA call in between (or a
- * different window range) makes fvo_ba_windows count again itself.  A window range whose match
- * maps exceed the LDS budget (the serial construction) is counted by fvo_ba_windows regardless. */
+ * fvo_ba_windows.  The next fvo_ba_windows call on this context with the same matches, n_matches,
+ * stereo, n_frames, first_end, n_windows and first_valid skips that step; the caller orders the
+ * two calls (the stream of fvo_ba_windows waits for this one's).  Any other BA call in between (or
+ * a different window range) makes fvo_ba_windows count again itself.  The caller must not change
+ * the contents of matches, n_matches or stereo between the two calls. */
 int fvo_ba_count_births(fvo_ctx* ctx, const int32_t* matches, const int32_t* n_matches, const float* stereo,
                         int32_t n_frames, int32_t cap, int32_t first_end, int32_t n_windows, int32_t first_valid,
                         fvo_stream stream);

@@ -181,3 +181,105 @@ def test_gpu_ba_window_20(K):
     p = ba_synth.clean_problem(n=K, seed=5, n_pts=2500)
     Tout, stats = _gpu_ba(p, first_end=K - 1, n_windows=1, window=K)
     _check(p, Tout[0], stats[0], 0, K - 1)
+
+
+# ---- the two homes of the forward match maps (csrc/ba.hip, problem construction).  The maps stay
+# in LDS when 2 (K-1) cap + cap <= 159744 bytes and cap < 65535, else they go to the window's global
+# workspace.  The two contexts of a comparison differ only in the keypoint capacity, no LM kernel
+# indexes by it, and a problem's content does not depend on cap (n_pts < cap), so the two modes
+# must agree bit for bit: the refined transforms, the stats, the exported landmarks, and the stats
+# of an iterations = 0 call (ids, initial landmarks and cost0, without the LM).
+_RUNS = {}
+
+
+def _run_full(gen, first_end, n_windows, window, ahead=False, **cfg):
+    """One context on clean_problem(**gen): ba_windows (after ba_count_births if `ahead`), every
+    window's landmarks, then ba_windows with iterations = 0.  Cached: tests share the runs."""
+    key = (tuple(sorted(gen.items())), first_end, n_windows, window, ahead, tuple(sorted(cfg.items())))
+    if key in _RUNS:
+        return _RUNS[key]
+    from forest_slam_amd import _lib
+    p = ba_synth.clean_problem(**gen)
+    ctx = _lib.Context(64, 64, max_batch=n_windows, stages=_lib.STAGE_BA, kp_capacity=gen["cap"], ba_window=window,
+                       **cfg)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    kp, nkp, m, nm, st, rel = (t(p[k]) for k in ("kp", "nkp", "matches", "nmatch", "stereo", "T_rel"))
+    if ahead:
+        ctx.ba_count_births(m, nm, st, first_end, n_windows, 0)
+    T, stats = ctx.ba_windows(kp, nkp, m, nm, st, rel, first_end, n_windows, 0, p["K"], p["B"], iterations=10)
+    lms = []
+    for w in range(n_windows):
+        xyz, cnt = ctx.ba_landmarks(w)
+        lms.append(xyz[:int(cnt.item())].cpu().numpy())
+    _, stats0 = ctx.ba_windows(kp, nkp, m, nm, st, rel, first_end, n_windows, 0, p["K"], p["B"], iterations=0)
+    torch.cuda.synchronize()
+    _RUNS[key] = dict(p=p, T=T.cpu().numpy(), stats=stats.cpu().numpy(), stats0=stats0.cpu().numpy(), lms=lms)
+    return _RUNS[key]
+
+
+def _assert_bitwise(a, b):
+    assert np.array_equal(a["T"], b["T"]) and np.array_equal(a["stats"], b["stats"])
+    assert np.array_equal(a["stats0"], b["stats0"])
+    assert len(a["lms"]) == len(b["lms"])
+    for xa, xb in zip(a["lms"], b["lms"]):
+        assert xa.shape == xb.shape and np.array_equal(xa, xb)
+
+
+_SLIDE = dict(n=7, n_pts=400, seed=11, drop=0.05)  # window 4: 7 * 24576 B > 159744 B at cap 24576
+
+
+@pytest.mark.gpu
+@pytest.mark.skipif(not gpu_available(), reason="needs a ROCm GPU")
+def test_gpu_ba_global_maps_sliding_windows():
+    """Maps in global memory: windows ending at frames 2..6 (the first of 3 frames), outlier matches."""
+    g = _run_full(dict(_SLIDE, cap=24576), first_end=2, n_windows=5, window=4)
+    counts = [(333, 946), (360, 1280), (355, 1269), (358, 1262), (356, 1243)]  # oracle/ba_ref.py on the CPU
+    for w in range(5):
+        e = 2 + w
+        _check(g["p"], g["T"][w], g["stats"][w], max(0, e - 3), e)
+        assert (g["stats"][w][2], g["stats"][w][3]) == counts[w]
+    _assert_bitwise(g, _run_full(dict(_SLIDE, cap=512), first_end=2, n_windows=5, window=4))
+
+
+@pytest.mark.gpu
+@pytest.mark.skipif(not gpu_available(), reason="needs a ROCm GPU")
+@pytest.mark.parametrize("cfg,counts", [(dict(ba_max_landmarks=100), (100, 374)), (dict(ba_max_obs=250), (65, 248))])
+def test_gpu_ba_global_maps_caps(cfg, counts):
+    """Maps in global memory: creation stops at the first candidate that does not fit."""
+    g = _run_full(dict(_SLIDE, cap=24576), first_end=6, n_windows=1, window=4, **cfg)
+    _check(g["p"], g["T"][0], g["stats"][0], 3, 6, lmax=cfg.get("ba_max_landmarks", 4096),
+           omax=cfg.get("ba_max_obs", 32768))
+    assert (g["stats"][0][2], g["stats"][0][3]) == counts
+    _assert_bitwise(g, _run_full(dict(_SLIDE, cap=512), first_end=6, n_windows=1, window=4, **cfg))
+
+
+@pytest.mark.gpu
+@pytest.mark.skipif(not gpu_available(), reason="needs a ROCm GPU")
+@pytest.mark.parametrize("cap", [65535, 70000])
+def test_gpu_ba_global_maps_large_capacity(cap):
+    """cap = 65535: an index would collide with the u16 maps' sentinel, so the maps are global though
+    they would fit in LDS; cap = 70000: the tracked flags alone take over 64 KiB of dynamic LDS."""
+    gen = dict(n=3, n_pts=300, seed=12)
+    g = _run_full(dict(gen, cap=cap), first_end=2, n_windows=1, window=3)
+    _check(g["p"], g["T"][0], g["stats"][0], 0, 2)
+    assert (g["stats"][0][2], g["stats"][0][3]) == (258, 774)
+    _assert_bitwise(g, _run_full(dict(gen, cap=512), first_end=2, n_windows=1, window=3))
+
+
+@pytest.mark.gpu
+@pytest.mark.skipif(not gpu_available(), reason="needs a ROCm GPU")
+def test_gpu_ba_global_maps_births_ahead():
+    """fvo_ba_count_births ahead of fvo_ba_windows with the maps in global memory: the results of
+    fvo_ba_windows alone on a fresh context."""
+    ahead = _run_full(dict(_SLIDE, cap=24576), first_end=2, n_windows=5, window=4, ahead=True)
+    _assert_bitwise(ahead, _run_full(dict(_SLIDE, cap=24576), first_end=2, n_windows=5, window=4))
+
+
+@pytest.mark.gpu
+@pytest.mark.skipif(not gpu_available(), reason="needs a ROCm GPU")
+def test_gpu_ba_window_21_map_modes():
+    """The K = 21 problem of test_gpu_ba_window_20 at cap = 4096 (41 * 4096 B > 159744 B: global maps)
+    and at cap = 3072 (125952 B: LDS maps)."""
+    gen = dict(n=21, seed=5, n_pts=2500)
+    _assert_bitwise(_run_full(dict(gen, cap=4096), first_end=20, n_windows=1, window=21),
+                    _run_full(dict(gen, cap=3072), first_end=20, n_windows=1, window=21))

@@ -13,7 +13,7 @@ def main():
             n = r["Kernel_Name"].replace("void ", "").replace("(anonymous namespace)::", "").split("(")[0]
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r.get("Stream_Id") or r.get("Queue_Id"), n))
     rows.sort()
-    # the last step: from the last k_ba_build / k_ba_births-like first kernel of the step
+    # the last step: from its first BA kernel (k_ba_stereo, ahead of the construction) on
     starts = [i for i, r in enumerate(rows) if r[3].startswith("k_ba_stereo")]
     rows = rows[starts[-1]:] if starts else rows
     t0 = rows[0][0]
