@@ -58,6 +58,8 @@ SIGNATURES = {
     "fvo_workspace_bytes": (ctypes.c_int64, [_P]),
     "fvo_orb_detect_compute": (ctypes.c_int, [_P, _P, _I, _L, _I, _P, _P, _P, _I, _P]),
     "fvo_bf_match": (ctypes.c_int, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
+    "fvo_bf_knn_match": (ctypes.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "fvo_bf_ratio_match": (ctypes.c_int, [_P, _P, _P, _P, _P, _I, _I, ctypes.c_double, _I, _P, _P, _P]),
     "fvo_sgbm": (ctypes.c_int, [_P, _P, _P, _I, _L, _I, _P, _P, _P]),
     "fvo_backproject": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _P, ctypes.c_double, _P, _P, _P, _P]),
     "fvo_pnp_ransac": (ctypes.c_int, [_P, _P, _P, _P, _I, _I, _P, _P, ctypes.c_float, ctypes.c_double, _I, _P, _P,
@@ -244,6 +246,34 @@ class Context:
             m, nm = out
         self._check(self.L.fvo_bf_match(self.h, _ptr(d0.contiguous()), _ptr(n0), _ptr(d1.contiguous()), _ptr(n1), B,
                                         cap, _ptr(m), _ptr(nm), _stream(self.device)))
+        return m, nm
+
+    def bf_knn_match(self, d0, n0, d1, n1, k, out=None):
+        """k nearest train descriptors per query row, no cross-check (fvo_bf_knn_match); d* u8
+        [B,cap,32], n* i32 [B] -> int32 [B,cap,k,2] rows of (trainIdx, distance) by ascending
+        (distance, trainIdx), (-1, -1) past the train set's size; rows >= n0 are not written."""
+        B, cap, k = d0.shape[0], d0.shape[1], int(k)
+        if out is None:
+            out = torch.empty((B, cap, max(k, 0), 2), dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or out.shape != (B, cap, k, 2) or not out.is_contiguous():
+            raise TypeError(f"bf_knn_match: out must be a contiguous int32 [{B},{cap},{k},2] tensor")
+        self._check(self.L.fvo_bf_knn_match(self.h, _ptr(d0.contiguous()), _ptr(n0), _ptr(d1.contiguous()), _ptr(n1),
+                                            B, cap, k, _ptr(out), _stream(self.device)))
+        return out
+
+    def bf_ratio_match(self, d0, n0, d1, n1, ratio, mutual=True, out=None):
+        """Lowe's ratio test on the two nearest neighbours (fvo_bf_ratio_match): rows (queryIdx,
+        trainIdx, distance) with float(d1) < ratio * float(d2); mutual=True also requires the
+        reverse nearest neighbour (a subset of bf_match's rows).  Buffers as for bf_match."""
+        B, cap = d0.shape[0], d0.shape[1]
+        if out is None:
+            m = torch.empty((B, cap, 3), dtype=torch.int32, device=self.device)
+            nm = torch.empty((B,), dtype=torch.int32, device=self.device)
+        else:
+            m, nm = out
+        self._check(self.L.fvo_bf_ratio_match(self.h, _ptr(d0.contiguous()), _ptr(n0), _ptr(d1.contiguous()), _ptr(n1),
+                                              B, cap, float(ratio), int(bool(mutual)), _ptr(m), _ptr(nm),
+                                              _stream(self.device)))
         return m, nm
 
     def sgbm(self, left, right, out=None, status=None):

@@ -41,6 +41,7 @@ enum FvoKernel {
   KN_ORB_HARRIS, KN_ORB_SELECT2, KN_ORB_OFFSETS, KN_ORB_ANGLE, KN_ORB_BLUR, KN_ORB_BRIEF, KN_BF_ARGMIN,
   KN_BF_FINISH, KN_SG_VERT, KN_SG_ROWS, KN_SG_MEDIAN, KN_BACKPROJECT, KN_PNP, KN_BA_STEREO,
   KN_BA_BUILD, KN_BA_SOLVE, KN_GATHER, KN_ESSENTIAL, KN_RECOVER, KN_INGEST, KN_MOTION_BLUR, KN_MAP_XFORM, KN_VOXEL,
+  KN_BF_KNN, KN_BF_RATIO,  // new ids go here: tests/sanitize/speckle_check.cpp pins the speckle names as the last four
   KN_SPK_LOCAL, KN_SPK_SEAMS, KN_SPK_SUM, KN_SPK_APPLY, KN_COUNT
 };
 
@@ -77,6 +78,7 @@ struct fvo_ctx {
   // BF workspace
   uint32_t* bf_rowkey = nullptr;  // [B][cap] (distance << 16 | train index) minimum per query row
   uint32_t* bf_colkey = nullptr;  // [B][cap] (distance << 16 | query index) minimum per train column
+  uint32_t* bf_knn = nullptr;     // [3][B][cap] ratio test: forward keys 1 and 2 per row, reverse key per column
   // SGBM workspace
   uint16_t* sg_V = nullptr;     // top-down path V, [B][HG4 + nstripes][width1][4][D] (4-row groups)
   uint16_t* sg_M = nullptr;     // min over d of each V row, [B][HG4 + nstripes][width1][4]
@@ -155,6 +157,11 @@ int orb_run(fvo_ctx* ctx, const uint8_t* images, int batch, int64_t image_stride
 int bf_init(fvo_ctx* ctx);
 int bf_run(fvo_ctx* ctx, const uint8_t* q, const int32_t* nq, const uint8_t* t, const int32_t* nt, int batch, int cap,
            int32_t* matches, int32_t* nmatch, hipStream_t s);
+// k-nearest neighbours / ratio test (bf.hip); arguments validated by bf_api.cpp
+int bf_knn_run(fvo_ctx* ctx, const uint8_t* q, const int32_t* nq, const uint8_t* t, const int32_t* nt, int batch,
+               int cap, int k, int32_t* knn, hipStream_t s);
+int bf_ratio_run(fvo_ctx* ctx, const uint8_t* q, const int32_t* nq, const uint8_t* t, const int32_t* nt, int batch,
+                 int cap, double ratio, int mutual, int32_t* matches, int32_t* nmatch, hipStream_t s);
 int sgbm_init(fvo_ctx* ctx);
 int sgbm_run(fvo_ctx* ctx, const uint8_t* L, const uint8_t* R, int batch, int64_t image_stride, int pitch,
              int16_t* disp, int32_t* status, hipStream_t s);

@@ -6,6 +6,8 @@ Face 1 mirrors the OpenCV calls of ros_ws/src/stereo_slam.py:
     bf = BFMatcher(NORM_HAMMING, crossCheck=True)               (:85)
     kps, desc = orb.detectAndCompute(img, None)                 (:232-233, :240-241)
     matches = bf.match(desc0, desc1)                            (:234, :242)
+      (and, beside the reference, DescriptorMatcher_create("BruteForce-Hamming").knnMatch(d0, d1, k)
+       for Lowe's ratio test)
     StereoSGBM_create(...).compute(L, R)                        (:108-117)
       (with OpenCV's speckleWindowSize / speckleRange post-filter, and filterSpeckles itself)
     ok, rvec, tvec, inliers = solvePnPRansac(P, p, K, dist, ...)  (:294-295)
@@ -149,14 +151,11 @@ def _desc_tensor(d, name):
     return t
 
 
-class BFMatcher:
-    """cv2.BFMatcher(NORM_HAMMING, crossCheck=True): mutual nearest neighbours by Hamming
-    distance, first index on ties, DMatch list in ascending queryIdx."""
+class _HammingMatcher:
+    """What the two brute-force Hamming matchers share: one BF-only context that grows with the
+    descriptor count, and the padded single-item batch the library takes."""
 
-    def __init__(self, normType=NORM_HAMMING, crossCheck=False):
-        if normType != NORM_HAMMING or not crossCheck:
-            raise NotImplementedError("BFMatcher: only NORM_HAMMING with crossCheck=True is implemented")
-        self._ctx = None
+    _ctx = None
 
     def _context(self, n):
         cap = max(1024, -(-n // 1024) * 1024)
@@ -164,12 +163,9 @@ class BFMatcher:
             self._ctx = _lib.Context(64, 64, max_batch=1, stages=_lib.STAGE_BF, kp_capacity=cap)
         return self._ctx
 
-    def matchDevice(self, d0: torch.Tensor, d1: torch.Tensor):
-        """Device-side variant: int32 [M,3] rows (queryIdx, trainIdx, distance)."""
+    def _batch(self, d0, d1):
         dev = _device()
         n0, n1 = d0.shape[0], d1.shape[0]
-        if n0 == 0 or n1 == 0:
-            return torch.empty((0, 3), dtype=torch.int32, device=dev)
         ctx = self._context(max(n0, n1))
         cap = ctx.kp_cap
         q = torch.zeros((1, cap, 32), dtype=torch.uint8, device=dev)
@@ -178,6 +174,35 @@ class BFMatcher:
         t[0, :n1] = d1.to(dev)
         nq = torch.tensor([n0], dtype=torch.int32, device=dev)
         nt = torch.tensor([n1], dtype=torch.int32, device=dev)
+        return ctx, q, nq, t, nt
+
+
+def _check_knn(name, k, mask):
+    if mask is not None:
+        raise NotImplementedError(f"{name}: mask is not implemented")
+    if int(k) < 1:
+        raise error(f"{name}: k must be >= 1")
+    if int(k) > 8:
+        raise NotImplementedError(f"{name}: k > 8 is not implemented")
+    return int(k)
+
+
+class BFMatcher(_HammingMatcher):
+    """cv2.BFMatcher(NORM_HAMMING, crossCheck=True): mutual nearest neighbours by Hamming
+    distance, first index on ties, DMatch list in ascending queryIdx."""
+
+    def __init__(self, normType=NORM_HAMMING, crossCheck=False):
+        if normType != NORM_HAMMING or not crossCheck:
+            raise NotImplementedError("BFMatcher: only NORM_HAMMING with crossCheck=True is implemented; the matcher "
+                                      'without cross-check is DescriptorMatcher_create("BruteForce-Hamming")')
+
+    def matchDevice(self, d0: torch.Tensor, d1: torch.Tensor):
+        """Device-side variant: int32 [M,3] rows (queryIdx, trainIdx, distance)."""
+        dev = _device()
+        n0, n1 = d0.shape[0], d1.shape[0]
+        if n0 == 0 or n1 == 0:
+            return torch.empty((0, 3), dtype=torch.int32, device=dev)
+        ctx, q, nq, t, nt = self._batch(d0, d1)
         m, nm = ctx.bf_match(q, nq, t, nt)
         return m[0, :int(nm[0].item())]
 
@@ -187,9 +212,58 @@ class BFMatcher:
         m = self.matchDevice(_desc_tensor(queryDescriptors, "query"), _desc_tensor(trainDescriptors, "train"))
         return [DMatch(r[0], r[1], 0, float(r[2])) for r in m.cpu().numpy()]
 
+    def knnMatch(self, queryDescriptors, trainDescriptors, k, mask=None, compactResult=False):
+        """With crossCheck=True cv2 allows k == 1 only: the cross-checked matches, one list per
+        query row, empty where the row has no mutual nearest neighbour."""
+        if _check_knn("BFMatcher.knnMatch", k, mask) != 1:
+            raise error("BFMatcher.knnMatch: crossCheck=True allows k == 1 only")
+        q = _desc_tensor(queryDescriptors, "query")
+        out = [[] for _ in range(q.shape[0])]
+        for r in self.matchDevice(q, _desc_tensor(trainDescriptors, "train")).cpu().numpy():
+            out[int(r[0])].append(DMatch(r[0], r[1], 0, float(r[2])))
+        return out
+
 
 def BFMatcher_create(normType=NORM_HAMMING, crossCheck=False):
     return BFMatcher(normType, crossCheck)
+
+
+DescriptorMatcher_BRUTEFORCE_HAMMING = 4
+
+
+class HammingDescriptorMatcher(_HammingMatcher):
+    """cv2.DescriptorMatcher_create("BruteForce-Hamming"): nearest neighbours by Hamming distance
+    without cross-check; equal distances keep ascending trainIdx.  The ratio-test idiom
+        good = [m for m, n in matcher.knnMatch(d0, d1, k=2) if m.distance < 0.75 * n.distance]
+    runs on it unchanged (rows with fewer than two neighbours do not unpack, as with cv2)."""
+
+    def knnMatchDevice(self, d0: torch.Tensor, d1: torch.Tensor, k: int):
+        """Device-side variant: int32 [n0,k,2] rows of (trainIdx, distance), (-1, -1) where the
+        train set has fewer than k descriptors."""
+        k = _check_knn("knnMatch", k, None)
+        dev = _device()
+        n0, n1 = d0.shape[0], d1.shape[0]
+        if n0 == 0 or n1 == 0:
+            return torch.full((n0, k, 2), -1, dtype=torch.int32, device=dev)
+        ctx, q, nq, t, nt = self._batch(d0, d1)
+        return ctx.bf_knn_match(q, nq, t, nt, k)[0, :n0]
+
+    def knnMatch(self, queryDescriptors, trainDescriptors, k, mask=None, compactResult=False):
+        k = _check_knn("knnMatch", k, mask)
+        knn = self.knnMatchDevice(_desc_tensor(queryDescriptors, "query"), _desc_tensor(trainDescriptors, "train"), k)
+        return [[DMatch(q, t, 0, float(d)) for t, d in row if t >= 0] for q, row in enumerate(knn.cpu().numpy())]
+
+    def match(self, queryDescriptors, trainDescriptors, mask=None):
+        if mask is not None:
+            raise NotImplementedError("match: mask is not implemented")
+        return [row[0] for row in self.knnMatch(queryDescriptors, trainDescriptors, 1) if row]
+
+
+def DescriptorMatcher_create(descriptorMatcherType):
+    if descriptorMatcherType not in ("BruteForce-Hamming", DescriptorMatcher_BRUTEFORCE_HAMMING):
+        raise NotImplementedError('DescriptorMatcher_create: only "BruteForce-Hamming" '
+                                  "(DescriptorMatcher_BRUTEFORCE_HAMMING) is implemented")
+    return HammingDescriptorMatcher()
 
 
 # --------------------------------------------------------------------------- StereoSGBM
@@ -487,12 +561,16 @@ class ORBMatching(torch.nn.Module):
     keypoints0/1 [N,2], scores0/1 [N], descriptors0/1 [32,N] (u8), matches0/1 [N] (int64,
     -1 unmatched) and matching_scores0/1 [N] (1 - distance/256), so `v[0]` picks image 0
     of the batch exactly as the reference does.  ORB + BF-cross-check underneath, one
-    batched launch per stage."""
+    batched launch per stage.  match_ratio (argument or config key) > 0 keeps only the
+    cross-checked matches that also pass Lowe's ratio test at that ratio."""
 
-    def __init__(self, config=None, nfeatures=500, **orb_params):
+    def __init__(self, config=None, nfeatures=500, match_ratio=0.0, **orb_params):
         super().__init__()
         cfg = dict(config or {})
         self.nfeatures = int(cfg.get("nfeatures", nfeatures))
+        self.match_ratio = float(cfg.get("match_ratio", match_ratio))
+        if not (np.isfinite(self.match_ratio) and self.match_ratio >= 0.0):
+            raise error("ORBMatching: match_ratio must be finite and >= 0")
         self.orb_params = orb_params
         self._cache = _CtxCache()
 
@@ -512,7 +590,10 @@ class ORBMatching(torch.nn.Module):
                                                               stages=_lib.STAGE_ORB | _lib.STAGE_BF,
                                                               **self.orb_params))
         kp, desc, cnt = ctx.orb(imgs)
-        m, nm = ctx.bf_match(desc[:B], cnt[:B], desc[B:], cnt[B:])
+        if self.match_ratio > 0.0:
+            m, nm = ctx.bf_ratio_match(desc[:B], cnt[:B], desc[B:], cnt[B:], self.match_ratio, mutual=True)
+        else:
+            m, nm = ctx.bf_match(desc[:B], cnt[:B], desc[B:], cnt[B:])
         cnt_h, nm_h, m_h = cnt.cpu(), nm.cpu(), m.cpu()
         out = {k: [] for k in ("keypoints0", "keypoints1", "scores0", "scores1", "descriptors0", "descriptors1",
                                "matches0", "matches1", "matching_scores0", "matching_scores1")}

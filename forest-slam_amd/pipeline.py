@@ -71,8 +71,10 @@ def _upload(msgs, dev):
 
 def run_stereo_bag(path: str, batch: int = 32, nfeatures: int = 500, frame_interval: int = 1, ba_window: int = 0,
                    device="cuda:0", K_left=K0, dist_left=DIST_L, K_right=K1, dist_right=DIST_R, baseline=BASELINE,
-                   point_map=None, speckle_window: int = 0, speckle_range: int = 0):
+                   point_map=None, speckle_window: int = 0, speckle_range: int = 0, match_ratio: float = 0.0):
     """stereo_slam.py's ORB branch over a bag -> (TUM rows f64[n,8], relative T, statuses).
+    match_ratio: > 0 keeps only the cross-checked matches that pass Lowe's ratio test at that
+    ratio (0 = the reference's matcher).
     speckle_window / speckle_range: StereoSGBM_create's speckleWindowSize / speckleRange (0 = off,
     the reference's get_disparity_map()).
     point_map: a ``mapping.PointMap`` that receives every posed frame's points3D in the map
@@ -83,7 +85,8 @@ def run_stereo_bag(path: str, batch: int = 32, nfeatures: int = 500, frame_inter
         return np.zeros((0, 8)), np.zeros((0, 4, 4)), np.zeros((0,), np.int32)
     H, W = pairs[0][1].height, pairs[0][1].width
     fe = vo.StereoFrontEnd(W, H, K_left, dist_left, baseline, batch=batch, nfeatures=nfeatures, device=device,
-                           ba_window=ba_window, speckle_window=speckle_window, speckle_range=speckle_range)
+                           ba_window=ba_window, speckle_window=speckle_window, speckle_range=speckle_range,
+                           match_ratio=match_ratio)
     ctx, dev = fe.ctx, fe.dev
 
     def gray(lo, hi):
@@ -118,14 +121,15 @@ def run_stereo_bag(path: str, batch: int = 32, nfeatures: int = 500, frame_inter
 
 
 def run_mono_bag(path: str, batch: int = 32, nfeatures: int = 500, frame_interval: int = 1, device="cuda:0",
-                 K=K0, dist=DIST_L, topic=LEFT):
-    """mono_slam.py's loop (ORB + BF + findEssentialMat + recoverPose) over a bag's left topic."""
+                 K=K0, dist=DIST_L, topic=LEFT, match_ratio: float = 0.0):
+    """mono_slam.py's loop (ORB + BF + findEssentialMat + recoverPose) over a bag's left topic.
+    match_ratio: as for run_stereo_bag."""
     bag = rosbag.Bag(path)
     sel = [(t, m) for index, (_, m, t) in enumerate(bag.read_messages(topics=[topic])) if index % frame_interval == 0]
     if len(sel) < 2:
         return np.zeros((0, 8)), np.zeros((0, 4, 4)), np.zeros((0,), np.int32)
     H, W = sel[0][1].height, sel[0][1].width
-    fe = vo.MonoFrontEnd(W, H, K, batch=batch, nfeatures=nfeatures, device=device)
+    fe = vo.MonoFrontEnd(W, H, K, batch=batch, nfeatures=nfeatures, device=device, match_ratio=match_ratio)
     ctx, dev = fe.ctx, fe.dev
     g0 = ctx.undistort_gray(_upload([sel[0][1]], dev), K, dist)
     fe.prime(g0[0])

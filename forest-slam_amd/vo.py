@@ -35,12 +35,29 @@ STATUS_KP_OVERFLOW = -3
 STATUS_SGBM_FAILED = -4
 
 
+def _match_ratio(match_ratio) -> float:
+    r = float(match_ratio)
+    if not (np.isfinite(r) and r >= 0.0):
+        raise ValueError("match_ratio must be finite and >= 0 (0 = cross-check only)")
+    return r
+
+
+def _match(ctx, match_ratio, d0, n0, d1, n1, out):
+    """The front ends' matcher: cross-checked nearest neighbours (the reference's BFMatcher), and
+    with match_ratio > 0 only those that also pass Lowe's ratio test against the runner-up.  The
+    mutual form keeps the matches injective in trainIdx, which the BA's landmark chaining needs."""
+    if match_ratio > 0.0:
+        return ctx.bf_ratio_match(d0, n0, d1, n1, match_ratio, mutual=True, out=out)
+    return ctx.bf_match(d0, n0, d1, n1, out=out)
+
+
 class StereoFrontEnd:
     def __init__(self, width: int, height: int, K: np.ndarray, dist: np.ndarray, baseline: float, batch: int,
                  nfeatures: int = 500, match_right: bool = True, device=None, ba_window: int = 10,
                  ba_iters: int = 10, overlap_sgbm: bool = False, sgbm_last: bool = False, births_ahead: bool = False,
-                 speckle_window: int = 0, speckle_range: int = 0, **params):
+                 speckle_window: int = 0, speckle_range: int = 0, match_ratio: float = 0.0, **params):
         self.B = batch
+        self.match_ratio = _match_ratio(match_ratio)
         self.K = np.asarray(K, np.float64)
         self.dist = np.resize(np.asarray(dist, np.float64), 5)
         self.baseline = float(baseline)
@@ -208,8 +225,8 @@ class StereoFrontEnd:
                               (self.q_kp[0], self.last_kp), (self.q_kp[1:n], kp[:n - 1]),
                               (self.sg_lastL, L[n - 1]), (self.sg_lastR, R[n - 1])])
             nb = 2 * n if self.match_right else n
-            m, nm = ctx.bf_match(self.q_desc[:nb], self.q_cnt[:nb], desc[:nb], cnt[:nb],
-                                 out=(self.matches[:nb], self.nmatch[:nb]))
+            m, nm = _match(ctx, self.match_ratio, self.q_desc[:nb], self.q_cnt[:nb], desc[:nb], cnt[:nb],
+                           out=(self.matches[:nb], self.nmatch[:nb]))
             ctx.copy_regions([(self.last_kp, kp[n - 1]), (self.last_desc[0], desc[n - 1]),
                               (self.last_desc[1], desc[2 * n - 1]), (self.last_cnt[0:1], cnt[n - 1:n]),
                               (self.last_cnt[1:2], cnt[2 * n - 1:2 * n])])
@@ -363,8 +380,10 @@ class MonoFrontEnd:
     cv2.recoverPose would raise; T is the identity there."""
 
     def __init__(self, width: int, height: int, K: np.ndarray, batch: int, nfeatures: int = 500, device=None,
-                 prob: float = 0.999, threshold: float = 1.0, overlap: bool = False, **params):
+                 prob: float = 0.999, threshold: float = 1.0, overlap: bool = False, match_ratio: float = 0.0,
+                 **params):
         self.B = batch
+        self.match_ratio = _match_ratio(match_ratio)
         self.K = np.asarray(K, np.float64)
         self.focal = float(self.K[0, 0])
         self.pp = (float(self.K[0, 2]), float(self.K[1, 2]))
@@ -455,7 +474,8 @@ class MonoFrontEnd:
             ctx.copy_regions([(self.q_kp[0], self.last_kp), (self.q_desc[0], self.last_desc),
                               (self.q_cnt[0:1], self.last_cnt), (self.q_kp[1:n], kp[:n - 1]),
                               (self.q_desc[1:n], desc[:n - 1]), (self.q_cnt[1:n], cnt[:n - 1])])
-            m, nm = ctx.bf_match(self.q_desc[:n], self.q_cnt[:n], desc, cnt, out=(self.matches[:n], self.nmatch[:n]))
+            m, nm = _match(ctx, self.match_ratio, self.q_desc[:n], self.q_cnt[:n], desc, cnt,
+                           out=(self.matches[:n], self.nmatch[:n]))
             ctx.copy_regions([(self.last_kp, kp[n - 1]), (self.last_desc, desc[n - 1]),
                               (self.last_cnt, cnt[n - 1:n])])
         if self.overlap:

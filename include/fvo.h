@@ -7,6 +7,9 @@
  *                              stereo_slam.py:84, :232-233, :240-241
  *   fvo_bf_match            <- cv2.BFMatcher(cv2.NORM_HAMMING, crossCheck=True).match(d0, d1)
  *                              stereo_slam.py:85, :234, :242 (+ the :235-238 gather)
+ *   fvo_bf_knn_match        <- cv2.DescriptorMatcher_create("BruteForce-Hamming").knnMatch(d0, d1, k)
+ *   fvo_bf_ratio_match      <- ... + [m for m, n in knn if m.distance < ratio * n.distance]
+ *                              (Lowe's ratio test; no reference counterpart)
  *   fvo_sgbm                <- cv2.StereoSGBM_create(numDisparities=96, minDisparity=0,
  *                              blockSize=7, P1=392, P2=1568, mode=SGBM_3WAY).compute(L, R)
  *                              stereo_slam.py:108-117 (get_disparity_map)
@@ -160,6 +163,28 @@ int fvo_orb_detect_compute(fvo_ctx* ctx, const uint8_t* images, int32_t batch, i
 int fvo_bf_match(fvo_ctx* ctx, const uint8_t* query, const int32_t* n_query, const uint8_t* train,
                  const int32_t* n_train, int32_t batch, int32_t cap, int32_t* matches, int32_t* n_matches,
                  fvo_stream stream);
+
+/* The k nearest train descriptors of every query descriptor, without cross-check
+ * (DescriptorMatcher.knnMatch(q, t, k) for NORM_HAMMING): row q's neighbours are the min(k, n_train)
+ * train indices with the smallest (distance, trainIdx), in that order -- equal distances keep
+ * ascending train index, batchDistance's strict-< insertion.  query/train/counts as for
+ * fvo_bf_match; 1 <= k <= FVO_BF_MAX_K.
+ * knn: [batch][cap][k][2] i32 = (trainIdx, distance); (-1, -1) where a row has fewer than k
+ *      neighbours; rows >= n_query are not written.
+ * Stateless: the call reads and leaves no context state (so does fvo_bf_ratio_match). */
+#define FVO_BF_MAX_K 8
+int fvo_bf_knn_match(fvo_ctx* ctx, const uint8_t* query, const int32_t* n_query, const uint8_t* train,
+                     const int32_t* n_train, int32_t batch, int32_t cap, int32_t k, int32_t* knn, fvo_stream stream);
+
+/* Lowe's ratio test on the two nearest neighbours (m, n = knnMatch(q, t, 2)[i]): query row q is
+ * kept iff it has two neighbours and (double)m.distance < ratio * (double)n.distance (one IEEE
+ * double multiply, strict compare: Python's `m.distance < ratio * n.distance`), and, with
+ * mutual != 0, q is also the nearest query of m.trainIdx (smallest (distance, queryIdx): the
+ * cross-check of fvo_bf_match), which makes the result a subset of fvo_bf_match's.
+ * ratio must be finite and > 0.  matches/n_matches exactly as fvo_bf_match. */
+int fvo_bf_ratio_match(fvo_ctx* ctx, const uint8_t* query, const int32_t* n_query, const uint8_t* train,
+                       const int32_t* n_train, int32_t batch, int32_t cap, double ratio, int32_t mutual,
+                       int32_t* matches, int32_t* n_matches, fvo_stream stream);
 
 /* StereoSGBM 3-way disparity (incl. the final 3x3 median) of `batch` rectified pairs.
  * disparity: [batch][height][width] i16, disparity*16, invalid = (min_disparity-1)*16.
