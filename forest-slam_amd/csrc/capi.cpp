@@ -114,8 +114,14 @@ int fvo_create(int device, const fvo_config* cfg, fvo_ctx** out) {
   const int st = c->cfg.stages;
   if (st & ~FVO_STAGE_ALL) { c->err = "unknown bits in stages"; return bail(-1); }
   if (cfg->max_batch < 1) { c->err = "max_batch must be >= 1"; return bail(-1); }
-  if ((st & (FVO_STAGE_ORB | FVO_STAGE_SGBM)) && (cfg->width < 64 || cfg->height < 64)) {
+  if ((st & FVO_STAGE_ORB) && (cfg->width < 64 || cfg->height < 64)) {
     c->err = "image size must be at least 64x64";
+    return bail(-1);
+  }
+  // SGBM alone: its kernels clamp rows to the stripe and to the image and have no use for a tall
+  // image (OpenCV takes any size); 32 rows is the smallest height the parity tests run
+  if ((st & FVO_STAGE_SGBM) && (cfg->width < 64 || cfg->height < 32)) {
+    c->err = "image size must be at least 64x32 for SGBM (64x64 with ORB)";
     return bail(-1);
   }
   if (!(st & FVO_STAGE_ORB) && (st & (FVO_STAGE_BF | FVO_STAGE_POSE | FVO_STAGE_BA | FVO_STAGE_MONO)) &&

@@ -72,7 +72,8 @@ typedef void* fvo_stream; /* hipStream_t */
 #define FVO_DESC_BYTES 32
 
 typedef struct fvo_config {
-  int32_t width, height; /* image size shared by every call on this context         */
+  int32_t width, height; /* image size shared by every call on this context: at least 64x64
+                            with the ORB stage, 64x32 with the SGBM stage alone           */
   int32_t max_batch;     /* max images (ORB) / pairs (BF, SGBM) / frames (pose) per call */
   /* cv2.ORB_create() parameters; defaults = OpenCV defaults (stereo_slam.py:84) */
   int32_t nfeatures;       /* 500 */

@@ -151,15 +151,23 @@ def bf_match(d0: np.ndarray, d1: np.ndarray):
 
 # ----------------------------------------------------------------------------- SGBM
 def sgbm(L: np.ndarray, R: np.ndarray, num_disp: int = 96, block: int = 7, P1: int = 392, P2: int = 1568,
-         min_disp: int = 0, raw: bool = False):
+         min_disp: int = 0, raw: bool = False, disp12_max_diff: int = 0, pre_filter_cap: int = 0,
+         stripes: int = 4, clipped: bool = False):
+    """StereoSGBM(3-way).compute + medianBlur(3).  disp12_max_diff <= 0 -> 1 and ftzero =
+    max(pre_filter_cap, 15) | 1 as in OpenCV; stripes restates OpenCV's fixed 4.  raw: also
+    the disparity before the median; clipped: also the number of aggregated costs S = L + R + V
+    that the 16-bit saturation clipped.  Returns out, or (out[, raw][, clipped])."""
     L = np.ascontiguousarray(L, dtype=np.uint8)
     R = np.ascontiguousarray(R, dtype=np.uint8)
     H, W = L.shape
     out = np.zeros((H, W), np.int16)
     rawo = np.zeros((H, W), np.int16)
-    lib().ref_sgbm(_p(L, _u8p), _p(R, _u8p), H, W, W, min_disp, num_disp, block, P1, P2, _p(out, _i16p),
-                   _p(rawo, _i16p))
-    return (out, rawo) if raw else out
+    nclip = ctypes.c_longlong(0)
+    lib().ref_sgbm_ex(_p(L, _u8p), _p(R, _u8p), H, W, W, int(min_disp), int(num_disp), int(block), int(P1), int(P2),
+                      int(disp12_max_diff), int(pre_filter_cap), int(stripes), _p(out, _i16p), _p(rawo, _i16p),
+                      ctypes.byref(nclip))
+    res = (out,) + ((rawo,) if raw else ()) + ((int(nclip.value),) if clipped else ())
+    return res if len(res) > 1 else out
 
 
 def sgbm_row_cost(L, R, y, num_disp=96):

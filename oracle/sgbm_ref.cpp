@@ -5,7 +5,8 @@
 //                         mode=cv2.STEREO_SGBM_MODE_SGBM_3WAY).compute(prevL, prevR)
 // i.e. OpenCV 4.x StereoSGBMImpl::compute -> computeDisparity3WaySGBM(nstripes = 4)
 // -> medianBlur(disp, 3).  Defaults: disp12MaxDiff 0 -> 1, preFilterCap 0 -> ftzero 15,
-// uniquenessRatio 0 (check off), speckleWindowSize 0 (no speckle filter).
+// uniquenessRatio 0 (check off), speckleWindowSize 0 (no speckle filter).  ref_sgbm_ex takes
+// disp12MaxDiff, preFilterCap and the stripe count as well (0, 0, 4: the defaults above).
 // Per stripe s (stripe_sz = ceil(H/4), overlap = blockSize/2 + 1 + ceil(0.1*stripe_sz)):
 //   * Birchfield-Tomasi pixel cost on (a) the x-Sobel response clipped to [-15,15]
 //     (+15) and (b) raw intensity >> 2; the two outer columns of both planes read 15;
@@ -82,8 +83,9 @@ static void pixel_cost_bt(const uint8_t* L, const uint8_t* R, int H, int W, int 
 
 static inline Cost sat(int v) { return (Cost)std::min(std::max(v, (int)SHRT_MIN), (int)SHRT_MAX); }
 
+// nclip (optional): how many entries of S = L + R + V the 16-bit saturation clipped.
 static void sgbm_3way(const uint8_t* L, const uint8_t* R, int H, int W, int stride, const SgbmParams& p,
-                      int16_t* disp) {
+                      int16_t* disp, long long* nclip = nullptr) {
   const int DISP_SHIFT = 4, DISP_SCALE = 1 << DISP_SHIFT;
   const int minD = p.minD, maxD = p.minD + p.numD, D = p.numD;
   const int minX1 = std::max(maxD, 0), maxX1 = W + std::min(minD, 0), width1 = maxX1 - minX1;
@@ -175,6 +177,7 @@ static void sgbm_3way(const uint8_t* L, const uint8_t* R, int H, int W, int stri
         }
         for (int d = 0; d < D; ++d) {
           Rb[d] = Rn[d];
+          if (nclip && (int)S[d] + Rb[d] + vb[d] > SHRT_MAX) ++*nclip;
           S[d] = sat((int)S[d] + Rb[d] + vb[d]);
           if (S[d] < minCost) { minCost = S[d]; best = d; }
         }
@@ -227,14 +230,30 @@ extern "C" {
 
 // StereoSGBM(3-way).compute(L, R) incl. the final 3x3 median.  disp_out: int16 [H*W].
 // raw_out (optional): the disparity before the median filter.
-void ref_sgbm(const uint8_t* L, const uint8_t* R, int H, int W, int stride, int minD, int numD, int block, int P1,
-              int P2, int16_t* disp_out, int16_t* raw_out) {
+// disp12MaxDiff <= 0 -> 1, ftzero = max(preFilterCap, 15) | 1 (StereoSGBMImpl::compute);
+// nstripes is OpenCV's fixed 4 unless the caller restates another count.  clipped_out
+// (optional): the number of aggregated costs S the 16-bit saturation clipped.
+void ref_sgbm_ex(const uint8_t* L, const uint8_t* R, int H, int W, int stride, int minD, int numD, int block, int P1,
+                 int P2, int disp12MaxDiff, int preFilterCap, int nstripes, int16_t* disp_out, int16_t* raw_out,
+                 long long* clipped_out) {
   SgbmParams p;
   p.minD = minD; p.numD = numD; p.block = block; p.P1 = P1; p.P2 = P2;
+  p.disp12MaxDiff = disp12MaxDiff > 0 ? disp12MaxDiff : 1;
+  p.ftzero = std::max(preFilterCap, 15) | 1;
+  p.nstripes = nstripes;
   std::vector<int16_t> raw((size_t)H * W);
-  sgbm_3way(L, R, H, W, stride, p, raw.data());
+  long long nclip = 0;
+  sgbm_3way(L, R, H, W, stride, p, raw.data(), &nclip);
   if (raw_out) std::copy(raw.begin(), raw.end(), raw_out);
+  if (clipped_out) *clipped_out = nclip;
   median3_s16(raw.data(), disp_out, H, W);
+}
+
+// The entry as it was before ref_sgbm_ex (its signature is kept: a front-end written against
+// it keeps working with this library): the reference's call, every further parameter default.
+void ref_sgbm(const uint8_t* L, const uint8_t* R, int H, int W, int stride, int minD, int numD, int block, int P1,
+              int P2, int16_t* disp_out, int16_t* raw_out) {
+  ref_sgbm_ex(L, R, H, W, stride, minD, numD, block, P1, P2, 0, 0, 4, disp_out, raw_out, nullptr);
 }
 
 // pixel cost + hsum for one row (debug / parity of the first kernel stage).
