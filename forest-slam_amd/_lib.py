@@ -86,6 +86,7 @@ SIGNATURES = {
     "fvo_motion_blur": (ctypes.c_int, [_P, _P, _I, _L, _I, _I, ctypes.c_double, _P, _P, _I, _P, _P, _L, _I, _P]),
     "fvo_test_retain_best": (ctypes.c_int, [_P, _P, _I, _I, _P, _P, _P]),
     "fvo_debug_buffer": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
+    "fvo_debug_copy": (ctypes.c_int, [_P, ctypes.c_int, _P, _L]),
     "fvo_kernel_count": (ctypes.c_int, []),
     "fvo_kernel_name": (ctypes.c_char_p, [ctypes.c_int]),
     "fvo_timing_enable": (ctypes.c_int, [_P, ctypes.c_uint64]),
@@ -599,16 +600,13 @@ class Context:
         return R, t, T, g
 
     def debug_buffer(self, which: int) -> torch.Tensor:
-        """Host copy (u8 CPU tensor) of an internal workspace buffer (fvo_debug_buffer)."""
+        """Host copy (u8 CPU tensor) of an internal workspace buffer (fvo_debug_buffer for the size,
+        fvo_debug_copy for the bytes)."""
         p = ctypes.c_void_p()
         nb = ctypes.c_int64()
         self._check(self.L.fvo_debug_buffer(self.h, which, ctypes.byref(p), ctypes.byref(nb)))
-        torch.cuda.synchronize(self.device)
         host = torch.empty((nb.value,), dtype=torch.uint8)
-        hip = ctypes.CDLL("libamdhip64.so")
-        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-        if hip.hipMemcpy(ctypes.c_void_p(host.data_ptr()), p, nb.value, 2) != 0:  # 2 = DeviceToHost
-            raise RuntimeError("hipMemcpy failed")
+        self._check(self.L.fvo_debug_copy(self.h, which, ctypes.c_void_p(host.data_ptr()), nb.value))
         return host
 
     def geometry(self):

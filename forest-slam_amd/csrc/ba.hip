@@ -47,7 +47,7 @@ struct BaCam {
   double fx, fy, cx, cy, b;
 };
 
-constexpr int kKMax = 21;
+constexpr int kKMax = kBaMaxWindow;
 // parallel problem construction scratch per window (ints): births per birth frame [kKMax],
 // their observations [kKMax], created landmarks / observations [2], observations per frame [kKMax]
 constexpr int kBldL = 0, kBldO = kKMax, kBldTot = 2 * kKMax, kBldF = 2 * kKMax + 2, kBldInts = 3 * kKMax + 2;
@@ -1610,9 +1610,8 @@ size_t solve_shm(int K) {
 }  // namespace
 
 int ba_init(fvo_ctx* ctx) {
+  // arguments and config were validated by capi.cpp
   const fvo_config& c = ctx->cfg;
-  if (c.ba_window < 3 || c.ba_window > kKMax) return fvo_fail(ctx, "ba_window must be in [3, 21]");
-  if (c.ba_max_landmarks < 1 || c.ba_max_obs < 2) return fvo_fail(ctx, "bad BA landmark / observation caps");
   BaDims d = make_dims(ctx);
   ctx->ba_win_bytes = d.win;
   char* p = nullptr;
@@ -1642,6 +1641,7 @@ int ba_init(fvo_ctx* ctx) {
 
 int ba_stereo_run(fvo_ctx* ctx, const int16_t* disp, const float* kp, const int32_t* nkp, int batch, int cap,
                   const double* K, double baseline, float* stereo, hipStream_t s) {
+  // arguments and config were validated by capi.cpp
   const double fxB = K[0] * baseline;
   FVO_TIMED(ctx, KN_BA_STEREO, s,
             hipLaunchKernelGGL(k_ba_stereo, dim3((cap + 255) / 256, batch), dim3(256), 0, s, disp, kp, nkp,
@@ -1692,12 +1692,7 @@ int ba_run(fvo_ctx* ctx, const float* kp, const int32_t* nkp, const int32_t* mat
            const float* stereo, const double* Trel, int nframes, int cap, int first_end, int nwin, int first_valid,
            const double* K, double baseline, const double* inv_sigma2, int nlev, int iters, double* Tout,
            double* stats, hipStream_t s) {
-  if (cap != ctx->kp_cap) return fvo_fail(ctx, "ba: cap must equal the context keypoint capacity");
-  if (nwin > ctx->cfg.max_batch) return fvo_fail(ctx, "ba: n_windows exceeds max_batch");
-  if (first_end < 1 || first_end + nwin > nframes) return fvo_fail(ctx, "ba: windows exceed the frame range");
-  if (first_valid < 0 || first_valid >= first_end) return fvo_fail(ctx, "ba: first_valid out of range");
-  if (nlev < 1 || nlev > FVO_MAX_LEVELS) return fvo_fail(ctx, "ba: bad level count");
-  if (iters < 0 || iters > 100) return fvo_fail(ctx, "ba: iterations out of range");
+  // arguments and config were validated by capi.cpp
   const BaDims d = make_dims(ctx);
   BaIn in{kp, nkp, matches, nmatch, reinterpret_cast<const float4*>(stereo), Trel, {}, nlev};
   for (int i = 0; i < nlev; ++i) in.isig2[i] = inv_sigma2[i];
@@ -1735,10 +1730,7 @@ int ba_run(fvo_ctx* ctx, const float* kp, const int32_t* nkp, const int32_t* mat
 // rows and the stereo points only); recorded so that call skips it
 int ba_births_run(fvo_ctx* ctx, const int32_t* matches, const int32_t* nmatch, const float* stereo, int nframes,
                   int cap, int first_end, int nwin, int first_valid, hipStream_t s) {
-  if (cap != ctx->kp_cap) return fvo_fail(ctx, "ba: cap must equal the context keypoint capacity");
-  if (nwin > ctx->cfg.max_batch) return fvo_fail(ctx, "ba: n_windows exceeds max_batch");
-  if (first_end < 1 || first_end + nwin > nframes) return fvo_fail(ctx, "ba: windows exceed the frame range");
-  if (first_valid < 0 || first_valid >= first_end) return fvo_fail(ctx, "ba: first_valid out of range");
+  // arguments and config were validated by capi.cpp
   const BaDims d = make_dims(ctx);
   BaIn in{nullptr, nullptr, matches, nmatch, reinterpret_cast<const float4*>(stereo), nullptr, {}, 1};
   ba_births_launch(in, ctx->ba_ws, d, nwin, first_end, first_valid, s);
@@ -1756,7 +1748,7 @@ int ba_births_run(fvo_ctx* ctx, const int32_t* matches, const int32_t* nmatch, c
 }
 
 int ba_export_run(fvo_ctx* ctx, int window, double* xyz, int32_t* count, hipStream_t s) {
-  if (window < 0 || window >= ctx->cfg.max_batch) return fvo_fail(ctx, "ba: window index out of range");
+  // arguments and config were validated by capi.cpp
   const BaDims d = make_dims(ctx);
   hipLaunchKernelGGL(k_ba_export, dim3(32), dim3(256), 0, s, ctx->ba_ws, d, window, xyz, count);
   FVO_LAUNCH_CHECK(ctx);

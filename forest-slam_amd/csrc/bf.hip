@@ -314,8 +314,8 @@ void knn_launch(const uint8_t* q, const int32_t* nq, const uint8_t* t, const int
 }  // namespace
 
 int bf_init(fvo_ctx* ctx) {
+  // arguments and config were validated by capi.cpp (check_bf_config: 16-bit indices in the keys)
   const int64_t n = (int64_t)ctx->cfg.max_batch * ctx->kp_cap;
-  if (ctx->kp_cap > 0xFFFF) return fvo_fail(ctx, "BF: kp_capacity must be <= 65535 (16-bit indices in the keys)");
   int rc;
   if ((rc = fvo_alloc(ctx, &ctx->bf_rowkey, n)) || (rc = fvo_alloc(ctx, &ctx->bf_colkey, n))) return rc;
   // the key arrays start (and are left by every k_bf_finish) at "no key"
@@ -328,8 +328,7 @@ int bf_init(fvo_ctx* ctx) {
 
 int bf_run(fvo_ctx* ctx, const uint8_t* q, const int32_t* nq, const uint8_t* t, const int32_t* nt, int batch, int cap,
            int32_t* matches, int32_t* nmatch, hipStream_t s) {
-  if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(t)) & 15)
-    return fvo_fail(ctx, "descriptor buffers must be 16-byte aligned");
+  // arguments and config were validated by capi.cpp
   const dim3 grid((cap + kRows - 1) / kRows, (cap + kChunk - 1) / kChunk, batch);
   FVO_TIMED(ctx, KN_BF_ARGMIN, s, hipLaunchKernelGGL(k_bf_pass, grid, dim3(kRows), 0, s, q, nq, t, nt, cap,
                                                      ctx->bf_rowkey, ctx->bf_colkey));
@@ -339,9 +338,9 @@ int bf_run(fvo_ctx* ctx, const uint8_t* q, const int32_t* nq, const uint8_t* t, 
   return 0;
 }
 
-// Arguments validated by bf_api.cpp.
 int bf_knn_run(fvo_ctx* ctx, const uint8_t* q, const int32_t* nq, const uint8_t* t, const int32_t* nt, int batch,
                int cap, int k, int32_t* knn, hipStream_t s) {
+  // arguments and config were validated by capi.cpp
   FVO_TIMED(ctx, KN_BF_KNN, s, {
     if (k == 1) knn_launch<1, false>(q, nq, t, nt, batch, cap, k, 0, knn, s);
     else if (k == 2) knn_launch<2, false>(q, nq, t, nt, batch, cap, k, 0, knn, s);
@@ -354,6 +353,7 @@ int bf_knn_run(fvo_ctx* ctx, const uint8_t* q, const int32_t* nq, const uint8_t*
 
 int bf_ratio_run(fvo_ctx* ctx, const uint8_t* q, const int32_t* nq, const uint8_t* t, const int32_t* nt, int batch,
                  int cap, double ratio, int mutual, int32_t* matches, int32_t* nmatch, hipStream_t s) {
+  // arguments and config were validated by capi.cpp
   const int64_t plane = (int64_t)ctx->cfg.max_batch * ctx->kp_cap;
   uint32_t* fwd = ctx->bf_knn;
   uint32_t* rev = mutual ? ctx->bf_knn + 2 * plane : nullptr;

@@ -1,10 +1,15 @@
-// extern "C" entry points of libfvo.so (include/fvo.h).  Thin: argument checks, context
-// lifetime, dispatch to the per-stage launchers.  No allocation in the hot calls.
+// Every extern "C" entry point of libfvo.so (include/fvo.h) and every refusal that depends only on
+// the arguments, fvo_config and host fields of fvo_ctx: config checks (check_<stage>_config, run by
+// fvo_create before the first allocation), argument checks, context lifetime, dispatch to the
+// per-stage launchers.  Host-only: links against tests/sanitize/host_stubs.cpp for the sanitizer
+// programs.  No allocation in the hot calls.
+#include <cmath>
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
 
 #include "fvo_internal.h"
+#include "sgbm_params.h"
 
 int fvo_fail(fvo_ctx* ctx, const std::string& msg) {
   if (ctx) ctx->err = msg;
@@ -83,18 +88,70 @@ void fvo_config_default(fvo_config* c, int32_t width, int32_t height) {
 }
 
 static void release(fvo_ctx* c) {
-  void* ptrs[] = {c->pyr,        c->blur,      c->score,     c->cand,     c->hel,
-                  c->ncand,      c->nsel1,     c->nsel2,     c->koff,     c->scratch, c->fast_rec, c->rt.xofs,  c->rt.xc1,
-                  c->rt.yofs,    c->rt.yc1,    c->umax,      c->bf_rowkey, c->bf_colkey, c->bf_knn, c->sg_ckpt,
-                  c->sg_V,      c->sg_M,      c->sg_raw,    c->sg_hand,   c->sg_ctl,    c->pnp_hyp,  c->pnp_good,
-                  c->pnp_sub,    c->rs_table, c->pnp_models, c->pnp_ws, c->pnp_state, c->pnp_plan, c->pnp_pts, c->ba_ws,
-                  c->em_x, c->em_models, c->em_good, c->em_nmod, c->em_state, c->em_ws};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
+  for (void* p : c->allocs) (void)hipFree(p);
   if (c->ba_s2) (void)hipStreamDestroy(c->ba_s2);
-
   if (c->ba_fork) (void)hipEventDestroy(c->ba_fork);
   if (c->ba_join) (void)hipEventDestroy(c->ba_join);
+}
+
+// ---- config checks, one per stage, in the order fvo_create runs the stage inits
+static int check_orb_config(fvo_ctx* ctx) {
+  const fvo_config& c = ctx->cfg;
+  if (c.nlevels < 1 || c.nlevels > FVO_MAX_LEVELS) return fvo_fail(ctx, "nlevels out of range");
+  if (c.first_level != 0 || c.wta_k != 2 || c.score_type != 0 || c.patch_size != 31)
+    return fvo_fail(ctx, "only firstLevel=0, WTA_K=2, HARRIS_SCORE, patchSize=31 are supported");
+  if (c.width > 4095 || c.height > 4095) return fvo_fail(ctx, "image dimensions must be < 4096");
+  // k_angle reads the whole 31x31 square around a keypoint unguarded; keypoints are kept
+  // edgeThreshold px inside the level, so it must cover the half patch (k_brief stages its
+  // rotated patch with REFLECT_101 and needs no such bound)
+  if (c.edge_threshold < c.patch_size / 2) return fvo_fail(ctx, "edgeThreshold must be >= patchSize/2 (15)");
+  return 0;
+}
+
+static int check_bf_config(fvo_ctx* ctx) {
+  if (ctx->kp_cap > 0xFFFF) return fvo_fail(ctx, "BF: kp_capacity must be <= 65535 (16-bit indices in the keys)");
+  return 0;
+}
+
+static int check_sgbm_config(fvo_ctx* ctx) {
+  const fvo_config& c = ctx->cfg;
+  if (c.block_size != 7) return fvo_fail(ctx, "SGBM: only blockSize=7 is supported");
+  if (c.num_disparities != 64 && c.num_disparities != 96 && c.num_disparities != 128)
+    return fvo_fail(ctx, "SGBM: numDisparities must be 64, 96 or 128");
+  if (c.uniqueness_ratio != 0) return fvo_fail(ctx, "SGBM: only uniquenessRatio=0 is supported");
+  if (c.sgbm_stripes < 1) return fvo_fail(ctx, "SGBM: stripes must be >= 1");
+  if (c.sgbm_mode != FVO_SGBM_CLASSIC && c.sgbm_mode != FVO_SGBM_LPATH)
+    return fvo_fail(ctx, "SGBM: sgbm_mode must be FVO_SGBM_CLASSIC or FVO_SGBM_LPATH");
+  if (c.sgbm_mode == FVO_SGBM_CLASSIC) {
+    const int g = sg_lanes(c), cb = sg_cols(c);
+    if (!((g == 4 && (cb == 32 || cb == 64)) || (g == 8 && (cb == 16 || cb == 32)) || (g == 16 && cb == 32)))
+      return fvo_fail(ctx, "SGBM: (sgbm_lanes, sgbm_cols) must be (4, 32|64), (8, 16|32) or (16, 32)");
+  } else if (c.sgbm_lanes != 0 || c.sgbm_cols != 0) {
+    return fvo_fail(ctx, "SGBM: sgbm_lanes / sgbm_cols apply to the classic schedule only (leave them 0)");
+  }
+  if (c.sgbm_handoff_us < -1) return fvo_fail(ctx, "SGBM: sgbm_handoff_us must be >= -1");
+  const SgParams p = make_params(c);
+  if (p.width1 <= 0) return fvo_fail(ctx, "SGBM: image narrower than numDisparities");
+  // path values are at most C + P2 with C <= 49 x the largest BT pixel cost (2 ftzero + 255/4);
+  // the kernels add P1 to them in u16 (min(a, b) + P1 for min(a + P1, b + P1)), so that sum
+  // must not wrap -- OpenCV's 16-bit CostType carries the same assumption
+  if (49 * (2 * p.ftzero + 63) + p.P2 + p.P1 > 0xFFFF)
+    return fvo_fail(ctx, "SGBM: P1/P2/preFilterCap too large for 16-bit path costs");
+  // the row pass sums S = L + R + V in u16 lanes and its WTA keys on S: each path is at most
+  // C + P2, so 3 (C + P2) must not wrap either
+  if (3 * (49 * (2 * p.ftzero + 63) + p.P2) > 0xFFFF)
+    return fvo_fail(ctx, "SGBM: P2/preFilterCap too large for the 16-bit aggregated cost");
+  // the L path's hand-off tags carry the column block in 7 bits
+  if (c.sgbm_mode == FVO_SGBM_LPATH && sg_nk(p) >= 128)
+    return fvo_fail(ctx, "SGBM: FVO_SGBM_LPATH needs width - numDisparities <= 4064 (use the classic schedule)");
+  return 0;
+}
+
+static int check_ba_config(fvo_ctx* ctx) {
+  const fvo_config& c = ctx->cfg;
+  if (c.ba_window < 3 || c.ba_window > kBaMaxWindow) return fvo_fail(ctx, "ba_window must be in [3, 21]");
+  if (c.ba_max_landmarks < 1 || c.ba_max_obs < 2) return fvo_fail(ctx, "bad BA landmark / observation caps");
+  return 0;
 }
 
 int fvo_create(int device, const fvo_config* cfg, fvo_ctx** out) {
@@ -130,6 +187,10 @@ int fvo_create(int device, const fvo_config* cfg, fvo_ctx** out) {
     return bail(-1);
   }
   c->kp_cap = cfg->kp_capacity > 0 ? cfg->kp_capacity : 2 * cfg->nfeatures + 64;
+  // (the POSE and MONO stages have no config of their own to check)
+  if (((st & FVO_STAGE_ORB) && check_orb_config(c)) || ((st & FVO_STAGE_BF) && check_bf_config(c)) ||
+      ((st & FVO_STAGE_SGBM) && check_sgbm_config(c)) || ((st & FVO_STAGE_BA) && check_ba_config(c)))
+    return bail(-1);
   int rc = 0;
   if (((st & FVO_STAGE_ORB) && (rc = orb_init(c))) || ((st & FVO_STAGE_BF) && (rc = bf_init(c))) ||
       ((st & FVO_STAGE_SGBM) && (rc = sgbm_init(c))) || ((st & FVO_STAGE_POSE) && (rc = pose_init(c))) ||
@@ -176,7 +237,41 @@ int fvo_bf_match(fvo_ctx* c, const uint8_t* query, const int32_t* n_query, const
   if (batch == 0) return 0;
   if (!query || !n_query || !train || !n_train || !matches || !n_matches) return fvo_fail(c, "null pointer argument");
   if (cap < 1 || cap > c->kp_cap) return fvo_fail(c, "cap must be in [1, fvo_kp_capacity()]");
+  if ((reinterpret_cast<uintptr_t>(query) | reinterpret_cast<uintptr_t>(train)) & 15)
+    return fvo_fail(c, "descriptor buffers must be 16-byte aligned");
   return bf_run(c, query, n_query, train, n_train, batch, cap, matches, n_matches, (hipStream_t)stream);
+}
+
+// The checks fvo_bf_knn_match and fvo_bf_ratio_match share; 1 = nothing to do (batch == 0), < 0 = refused.
+static int bf_check(fvo_ctx* c, const void* query, const void* n_query, const void* train, const void* n_train,
+                    int32_t batch, int32_t cap) {
+  if (check_batch(c, batch, FVO_STAGE_BF)) return -1;
+  if (batch == 0) return 1;
+  if (!query || !n_query || !train || !n_train) return fvo_fail(c, "null pointer argument");
+  if (cap < 1 || cap > c->kp_cap) return fvo_fail(c, "cap must be in [1, fvo_kp_capacity()]");
+  if ((reinterpret_cast<uintptr_t>(query) | reinterpret_cast<uintptr_t>(train)) & 15)
+    return fvo_fail(c, "descriptor buffers must be 16-byte aligned");
+  return 0;
+}
+
+int fvo_bf_knn_match(fvo_ctx* c, const uint8_t* query, const int32_t* n_query, const uint8_t* train,
+                     const int32_t* n_train, int32_t batch, int32_t cap, int32_t k, int32_t* knn, fvo_stream stream) {
+  const int rc = bf_check(c, query, n_query, train, n_train, batch, cap);
+  if (rc) return rc < 0 ? rc : 0;
+  if (k < 1 || k > FVO_BF_MAX_K) return fvo_fail(c, "bf_knn_match: k must be in [1, 8]");
+  if (!knn) return fvo_fail(c, "null pointer argument");
+  return bf_knn_run(c, query, n_query, train, n_train, batch, cap, k, knn, (hipStream_t)stream);
+}
+
+int fvo_bf_ratio_match(fvo_ctx* c, const uint8_t* query, const int32_t* n_query, const uint8_t* train,
+                       const int32_t* n_train, int32_t batch, int32_t cap, double ratio, int32_t mutual,
+                       int32_t* matches, int32_t* n_matches, fvo_stream stream) {
+  const int rc = bf_check(c, query, n_query, train, n_train, batch, cap);
+  if (rc) return rc < 0 ? rc : 0;
+  if (!matches || !n_matches) return fvo_fail(c, "null pointer argument");
+  if (!std::isfinite(ratio) || ratio <= 0.0) return fvo_fail(c, "bf_ratio_match: ratio must be finite and > 0");
+  return bf_ratio_run(c, query, n_query, train, n_train, batch, cap, ratio, mutual != 0, matches, n_matches,
+                      (hipStream_t)stream);
 }
 
 int fvo_sgbm(fvo_ctx* c, const uint8_t* left, const uint8_t* right, int32_t batch, int64_t image_stride,
@@ -188,6 +283,35 @@ int fvo_sgbm(fvo_ctx* c, const uint8_t* left, const uint8_t* right, int32_t batc
   if (batch > (c->cfg.sgbm_max_batch > 0 ? c->cfg.sgbm_max_batch : c->cfg.max_batch))
     return fvo_fail(c, "batch exceeds sgbm_max_batch");
   return sgbm_run(c, left, right, batch, image_stride, pitch, disparity, status, (hipStream_t)stream);
+}
+
+int64_t fvo_speckle_workspace_bytes(int32_t batch, int32_t height, int32_t width) {
+  if (batch < 0 || height < 1 || width < 1) return -1;
+  const int64_t hw = (int64_t)height * width;
+  if (hw > INT32_MAX) return -1;  // labels are int32 pixel indices
+  if (batch == 0) return 0;
+  if (hw > INT64_MAX / 8 / batch) return -1;
+  return 8 * hw * batch;  // label + size plane, int32 each
+}
+
+int fvo_filter_speckles(fvo_ctx* c, int16_t* disparity, int32_t batch, int32_t height, int32_t width,
+                        int64_t image_stride, int32_t pitch, int32_t new_val, int32_t max_speckle_size,
+                        int32_t max_diff, void* workspace, int64_t workspace_bytes, fvo_stream stream) {
+  if (!c) return -1;
+  if (batch < 0 || batch > c->cfg.max_batch) return fvo_fail(c, "batch exceeds max_batch");
+  if (batch == 0) return 0;
+  if (!disparity || !workspace) return fvo_fail(c, "null pointer argument");
+  if (height < 1 || width < 1) return fvo_fail(c, "filter_speckles: height and width must be >= 1");
+  if ((int64_t)height * width > INT32_MAX) return fvo_fail(c, "filter_speckles: height*width exceeds INT32_MAX");
+  if (pitch < width || image_stride < (int64_t)pitch * height) return fvo_fail(c, "bad pitch/stride");
+  if (new_val < INT16_MIN || new_val > INT16_MAX) return fvo_fail(c, "filter_speckles: new_val outside int16");
+  if (max_diff < 0) return fvo_fail(c, "filter_speckles: max_diff < 0");
+  const int64_t need = fvo_speckle_workspace_bytes(batch, height, width);
+  if (need < 0 || workspace_bytes < need) return fvo_fail(c, "filter_speckles: workspace too small");
+  if (reinterpret_cast<uintptr_t>(workspace) & 3) return fvo_fail(c, "filter_speckles: workspace must be 4-byte aligned");
+  if (max_speckle_size <= 0) return 0;  // cv2: nothing is a speckle
+  return speckle_run(c, disparity, batch, height, width, image_stride, pitch, new_val, max_speckle_size, max_diff,
+                     workspace, (hipStream_t)stream);
 }
 
 int fvo_backproject(fvo_ctx* c, const int16_t* disparity, const float* kp0, const float* kp1, const int32_t* matches,
@@ -211,8 +335,9 @@ int fvo_pnp_ransac(fvo_ctx* c, const float* points3d, const float* points2d, con
   if (!points3d || !points2d || !n_points || !K || !dist || !rvec || !tvec || !T || !status)
     return fvo_fail(c, "null pointer argument");
   if (cap < 1) return fvo_fail(c, "cap must be >= 1");
-  if (iterations < 1 || iterations > c->pnp_max_iters) return fvo_fail(c, "iterations out of range");
+  if (iterations < 1 || iterations > kRansacMaxIters) return fvo_fail(c, "iterations out of range");
   if (!(confidence > 0 && confidence < 1)) return fvo_fail(c, "confidence must be in (0,1)");
+  if (cap > c->kp_cap) return fvo_fail(c, "pnp: cap exceeds the context keypoint capacity");
   return pnp_run(c, points3d, points2d, n_points, batch, cap, K, dist, reprojection_error, confidence, iterations,
                  rvec, tvec, T, status, inliers, (hipStream_t)stream);
 }
@@ -228,6 +353,15 @@ int fvo_keypoint_stereo(fvo_ctx* c, const int16_t* disparity, const float* keypo
   return ba_stereo_run(c, disparity, keypoints, n_keypoints, batch, cap, K, baseline, stereo, (hipStream_t)stream);
 }
 
+// The window range fvo_ba_windows and fvo_ba_count_births share (n_windows <= max_batch: check_batch).
+static int check_ba_range(fvo_ctx* c, int32_t n_frames, int32_t cap, int32_t first_end, int32_t n_windows,
+                          int32_t first_valid) {
+  if (cap != c->kp_cap) return fvo_fail(c, "ba: cap must equal the context keypoint capacity");
+  if (first_end < 1 || first_end + n_windows > n_frames) return fvo_fail(c, "ba: windows exceed the frame range");
+  if (first_valid < 0 || first_valid >= first_end) return fvo_fail(c, "ba: first_valid out of range");
+  return 0;
+}
+
 int fvo_ba_windows(fvo_ctx* c, const float* keypoints, const int32_t* n_keypoints, const int32_t* matches,
                    const int32_t* n_matches, const float* stereo, const double* T_rel, int32_t n_frames,
                    int32_t cap, int32_t first_end, int32_t n_windows, int32_t first_valid, const double* K,
@@ -239,6 +373,9 @@ int fvo_ba_windows(fvo_ctx* c, const float* keypoints, const int32_t* n_keypoint
       !stats)
     return fvo_fail(c, "null pointer argument");
   if (reinterpret_cast<uintptr_t>(stereo) & 15) return fvo_fail(c, "stereo buffer must be 16-byte aligned");
+  if (check_ba_range(c, n_frames, cap, first_end, n_windows, first_valid)) return -1;
+  if (n_levels < 1 || n_levels > FVO_MAX_LEVELS) return fvo_fail(c, "ba: bad level count");
+  if (iterations < 0 || iterations > 100) return fvo_fail(c, "ba: iterations out of range");
   return ba_run(c, keypoints, n_keypoints, matches, n_matches, stereo, T_rel, n_frames, cap, first_end, n_windows,
                 first_valid, K, baseline, inv_sigma2, n_levels, iterations, T_out, stats, (hipStream_t)stream);
 }
@@ -251,6 +388,7 @@ int fvo_ba_count_births(fvo_ctx* c, const int32_t* matches, const int32_t* n_mat
   if (n_windows == 0) return 0;
   if (!matches || !n_matches || !stereo) return fvo_fail(c, "null pointer argument");
   if (reinterpret_cast<uintptr_t>(stereo) & 15) return fvo_fail(c, "stereo buffer must be 16-byte aligned");
+  if (check_ba_range(c, n_frames, cap, first_end, n_windows, first_valid)) return -1;
   return ba_births_run(c, matches, n_matches, stereo, n_frames, cap, first_end, n_windows, first_valid,
                        (hipStream_t)stream);
 }
@@ -258,6 +396,7 @@ int fvo_ba_count_births(fvo_ctx* c, const int32_t* matches, const int32_t* n_mat
 int fvo_ba_landmarks(fvo_ctx* c, int32_t window, double* xyz, int32_t* count, fvo_stream stream) {
   if (check_batch(c, 1, FVO_STAGE_BA)) return -1;
   if (!xyz || !count) return fvo_fail(c, "null pointer argument");
+  if (window < 0 || window >= c->cfg.max_batch) return fvo_fail(c, "ba: window index out of range");
   return ba_export_run(c, window, xyz, count, (hipStream_t)stream);
 }
 
@@ -280,6 +419,9 @@ int fvo_find_essential(fvo_ctx* c, const float* p0, const float* p1, const int32
   if (!p0 || !p1 || !n_points || !E || !status) return fvo_fail(c, "null pointer argument");
   if (cap < 1 || cap > c->kp_cap) return fvo_fail(c, "cap must be in [1, fvo_kp_capacity()]");
   if (!(focal > 0.0)) return fvo_fail(c, "focal must be > 0");
+  if (max_iters < 1 || max_iters > kRansacMaxIters) return fvo_fail(c, "essential: max_iters out of range");
+  // k_em_hyp stages a frame's normalised points in LDS
+  if (cap > kEmMaxCap) return fvo_fail(c, "essential: point capacity exceeds LDS (cap <= 5040)");
   return essential_run(c, p0, p1, n_points, batch, cap, focal, cx, cy, prob, threshold, max_iters, E, mask, status,
                        (hipStream_t)stream);
 }
@@ -324,6 +466,10 @@ int fvo_motion_blur(fvo_ctx* c, const uint8_t* img, int32_t batch, int64_t src_s
   if (src_pitch < W || src_stride < (int64_t)src_pitch * H || dst_pitch < W || dst_stride < (int64_t)dst_pitch * H)
     return fvo_fail(c, "bad pitch/stride");
   if (img == out) return fvo_fail(c, "motion blur: out must not alias img");
+  // k_mb_fix rewrites the mask a dword at a time: refuse a misaligned mask before any launch,
+  // so an error never leaves the mask in its intermediate (seed / dilated bit) encoding
+  if (centers_cap > 0 && (reinterpret_cast<uintptr_t>(mask) & 3))
+    return fvo_fail(c, "motion blur: mask must be 4-byte aligned");
   return motion_blur_run(c, img, batch, src_stride, src_pitch, ksize, centers, n_centers, centers_cap, mask, out,
                          dst_stride, dst_pitch, (hipStream_t)stream);
 }
@@ -406,19 +552,18 @@ int fvo_voxel_down_sample(fvo_ctx* c, const double* points, int64_t n_points, do
     return 0;
   }
   if (workspace_bytes < 0) return fvo_fail(c, "workspace_bytes < 0");
-  return voxel_run(c, points, n_points, voxel_size, workspace, (size_t)workspace_bytes, out, n_out, status,
-                   (hipStream_t)stream);
+  const int64_t need = voxel_workspace_bytes(n_points);  // voxel_run's layout total
+  if (need < 0) return fvo_fail(c, "voxel_down_sample: workspace size query failed");
+  if (workspace_bytes < need) return fvo_fail(c, "voxel_down_sample: workspace too small");
+  return voxel_run(c, points, n_points, voxel_size, workspace, out, n_out, status, (hipStream_t)stream);
 }
 
 int fvo_kernel_count(void) { return KN_COUNT; }
 
 const char* fvo_kernel_name(int id) {
-  static const char* names[KN_COUNT] = {
-      "orb_copy_level0", "orb_resize", "orb_fast_score", "orb_nms_count", "orb_row_scan", "orb_nms_compact",
-      "orb_select_fast", "orb_harris", "orb_select_harris", "orb_offsets", "orb_angle", "orb_blur", "orb_brief",
-      "bf_argmin", "bf_finish", "sgbm_vert", "sgbm_rows", "sgbm_median", "backproject",
-      "pnp_ransac", "ba_stereo", "ba_build", "ba_solve", "gather_matches", "essential_ransac", "recover_pose", "ingest_undistort_gray", "motion_blur", "map_transform", "voxel_down_sample",
-      "bf_knn", "bf_ratio", "speckle_local", "speckle_seams", "speckle_sum", "speckle_apply"};
+#define FVO_KERNEL_NAME(id, name) name,
+  static const char* names[KN_COUNT] = {FVO_KERNELS(FVO_KERNEL_NAME)};
+#undef FVO_KERNEL_NAME
   return (id >= 0 && id < KN_COUNT) ? names[id] : "";
 }
 
@@ -455,9 +600,11 @@ int fvo_debug_buffer(fvo_ctx* c, int which, void** ptr, int64_t* bytes) {
   switch (which) {
     case 0: *ptr = c->pyr; *bytes = B * c->g.total_px; return 0;
     case 1:  // computed on request from the last call's pyramid (not part of the hot path)
+      if (!c->pyr) return fvo_fail(c, "orb stage not enabled");
       if (orb_blur_debug(c)) return -1;
       *ptr = c->blur; *bytes = B * c->g.total_px; return 0;
     case 2:  // computed on request from the last call's pyramid (not part of the hot path)
+      if (!c->pyr) return fvo_fail(c, "orb stage not enabled");
       if (orb_score_debug(c)) return -1;
       *ptr = c->score; *bytes = B * c->g.total_px; return 0;
     case 3: *ptr = c->ncand; *bytes = B * c->g.nlevels * 4; return 0;
@@ -471,6 +618,23 @@ int fvo_debug_buffer(fvo_ctx* c, int which, void** ptr, int64_t* bytes) {
       *ptr = c->sg_ctl; *bytes = (4 + B) * 4; return 0;
     default: return fvo_fail(c, "unknown debug buffer");
   }
+}
+
+int fvo_debug_copy(fvo_ctx* c, int which, void* host_dst, int64_t bytes) {
+  void* src = nullptr;
+  int64_t have = 0;
+  if (fvo_debug_buffer(c, which, &src, &have)) return -1;
+  if (!host_dst) return fvo_fail(c, "null pointer argument");
+  if (bytes < 0 || bytes > have) return fvo_fail(c, "debug_copy: bytes outside [0, the buffer's size]");
+  FVO_HIP(c, hipSetDevice(c->device));
+  FVO_HIP(c, hipDeviceSynchronize());
+  FVO_HIP(c, hipMemcpy(host_dst, src, (size_t)bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int fvo_test_retain_best(fvo_ctx* c, const float* keys, int32_t n, int32_t keep, int32_t* idx_out, int32_t* n_out,
+                         fvo_stream stream) {
+  return orb_retain_best_run(c, keys, n, keep, idx_out, n_out, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1088,7 +1088,8 @@ __global__ __launch_bounds__(256) void k_em_recover(const double* __restrict__ E
 }  // namespace
 
 int mono_init(fvo_ctx* ctx) {
-  ctx->em_max_iters = 1000;
+  // arguments and config were validated by capi.cpp
+  ctx->em_max_iters = kRansacMaxIters;
   const int64_t B = ctx->cfg.max_batch, it = B * ctx->em_max_iters;
   int rc;
   if ((rc = fvo_alloc(ctx, &ctx->em_x, B * ctx->kp_cap * 4)) || (rc = ransac_table_init(ctx)) ||
@@ -1101,6 +1102,7 @@ int mono_init(fvo_ctx* ctx) {
 
 int gather_run(fvo_ctx* ctx, const float* kp0, const float* kp1, const int32_t* matches, const int32_t* nmatch,
                int batch, int cap, float* p0, float* p1, int32_t* npts, hipStream_t s) {
+  // arguments and config were validated by capi.cpp
   FVO_TIMED(ctx, KN_GATHER, s, hipLaunchKernelGGL(k_gather_matches, dim3(batch), dim3(256), 0, s, kp0, kp1, matches,
                                                   nmatch, cap, p0, p1, npts));
   FVO_LAUNCH_CHECK(ctx);
@@ -1110,15 +1112,13 @@ int gather_run(fvo_ctx* ctx, const float* kp0, const float* kp1, const int32_t* 
 int essential_run(fvo_ctx* ctx, const float* p0, const float* p1, const int32_t* npts, int batch, int cap,
                   double focal, double cx, double cy, double prob, double threshold, int maxIters, double* E,
                   uint8_t* mask, int32_t* status, hipStream_t s) {
-  if (cap > ctx->kp_cap) return fvo_fail(ctx, "essential: cap exceeds the context keypoint capacity");
-  if (maxIters < 1 || maxIters > ctx->em_max_iters || maxIters > ctx->rs_table_iters)
-    return fvo_fail(ctx, "essential: max_iters out of range");
+  // arguments and config were validated by capi.cpp
   Pinhole K{focal, cx, cy};
   const double thr = threshold / ((focal + focal) / 2);
   const float thr2 = (float)(thr * thr);
   EmState* st = (EmState*)ctx->em_state;
   const size_t shm = (size_t)cap * 4 * sizeof(double);
-  if (shm + 640 * sizeof(int) > 160 * 1024) return fvo_fail(ctx, "essential: point capacity exceeds LDS (cap <= 5040)");
+  static_assert((size_t)kEmMaxCap * 4 * sizeof(double) + 640 * sizeof(int) == 160 * 1024, "kEmMaxCap: k_em_hyp's LDS");
   if (shm > 64 * 1024)
     FVO_HIP(ctx, hipFuncSetAttribute((const void*)k_em_hyp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
   // round 1: the first 128 subsets of every frame (the adaptive bound usually ends below)
@@ -1149,7 +1149,7 @@ int essential_run(fvo_ctx* ctx, const float* p0, const float* p1, const int32_t*
 int recover_run(fvo_ctx* ctx, const double* E, const int32_t* est, const float* p0, const float* p1,
                 const int32_t* npts, int batch, int cap, double focal, double cx, double cy, double dist, double* R,
                 double* t, double* T, int32_t* ngood, hipStream_t s) {
-  if (cap > ctx->kp_cap) return fvo_fail(ctx, "recover_pose: cap exceeds the context keypoint capacity");
+  // arguments and config were validated by capi.cpp
   Pinhole K{focal, cx, cy};
   // normalised points (the recoverPose normalisation equals findEssentialMat's)
   FVO_TIMED(ctx, KN_RECOVER, s, {

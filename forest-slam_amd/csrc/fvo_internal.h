@@ -35,15 +35,29 @@ struct ResizeTab {
   int64_t xoff[FVO_MAX_LEVELS], yoff[FVO_MAX_LEVELS];
 };
 
-// Kernel ids for the optional per-launch event timing (fvo_timing_enable / _read).
-enum FvoKernel {
-  KN_ORB_COPY, KN_ORB_RESIZE, KN_ORB_FAST, KN_ORB_NMS_COUNT, KN_ORB_ROW_SCAN, KN_ORB_COMPACT, KN_ORB_SELECT1,
-  KN_ORB_HARRIS, KN_ORB_SELECT2, KN_ORB_OFFSETS, KN_ORB_ANGLE, KN_ORB_BLUR, KN_ORB_BRIEF, KN_BF_ARGMIN,
-  KN_BF_FINISH, KN_SG_VERT, KN_SG_ROWS, KN_SG_MEDIAN, KN_BACKPROJECT, KN_PNP, KN_BA_STEREO,
-  KN_BA_BUILD, KN_BA_SOLVE, KN_GATHER, KN_ESSENTIAL, KN_RECOVER, KN_INGEST, KN_MOTION_BLUR, KN_MAP_XFORM, KN_VOXEL,
-  KN_BF_KNN, KN_BF_RATIO,  // new ids go here: tests/sanitize/speckle_check.cpp pins the speckle names as the last four
-  KN_SPK_LOCAL, KN_SPK_SEAMS, KN_SPK_SUM, KN_SPK_APPLY, KN_COUNT
-};
+// Limits that capi.cpp checks and a device file depends on (the device file static_asserts them).
+constexpr int kBaMaxWindow = 21;        // ba.hip kKMax: frames of a BA window
+constexpr int kEmMaxCap = 5040;         // essential.hip: points of one frame that fit k_em_hyp's LDS
+constexpr int kRansacMaxIters = 1000;   // pose.hip / essential.hip: hypothesis buffers, the subset table
+
+// Kernel ids for the optional per-launch event timing (fvo_timing_enable / _read) and their names
+// (fvo_kernel_name), in id order.
+#define FVO_KERNELS(X)                                                                                    \
+  X(KN_ORB_COPY, "orb_copy_level0") X(KN_ORB_RESIZE, "orb_resize") X(KN_ORB_FAST, "orb_fast_score")       \
+  X(KN_ORB_NMS_COUNT, "orb_nms_count") X(KN_ORB_ROW_SCAN, "orb_row_scan") X(KN_ORB_COMPACT, "orb_nms_compact") \
+  X(KN_ORB_SELECT1, "orb_select_fast") X(KN_ORB_HARRIS, "orb_harris") X(KN_ORB_SELECT2, "orb_select_harris") \
+  X(KN_ORB_OFFSETS, "orb_offsets") X(KN_ORB_ANGLE, "orb_angle") X(KN_ORB_BLUR, "orb_blur")                \
+  X(KN_ORB_BRIEF, "orb_brief") X(KN_BF_ARGMIN, "bf_argmin") X(KN_BF_FINISH, "bf_finish")                  \
+  X(KN_SG_VERT, "sgbm_vert") X(KN_SG_ROWS, "sgbm_rows") X(KN_SG_MEDIAN, "sgbm_median")                    \
+  X(KN_BACKPROJECT, "backproject") X(KN_PNP, "pnp_ransac") X(KN_BA_STEREO, "ba_stereo")                   \
+  X(KN_BA_BUILD, "ba_build") X(KN_BA_SOLVE, "ba_solve") X(KN_GATHER, "gather_matches")                    \
+  X(KN_ESSENTIAL, "essential_ransac") X(KN_RECOVER, "recover_pose") X(KN_INGEST, "ingest_undistort_gray") \
+  X(KN_MOTION_BLUR, "motion_blur") X(KN_MAP_XFORM, "map_transform") X(KN_VOXEL, "voxel_down_sample")      \
+  X(KN_BF_KNN, "bf_knn") X(KN_BF_RATIO, "bf_ratio") X(KN_SPK_LOCAL, "speckle_local")                      \
+  X(KN_SPK_SEAMS, "speckle_seams") X(KN_SPK_SUM, "speckle_sum") X(KN_SPK_APPLY, "speckle_apply")
+#define FVO_KERNEL_ID(id, name) id,
+enum FvoKernel { FVO_KERNELS(FVO_KERNEL_ID) KN_COUNT };
+#undef FVO_KERNEL_ID
 
 struct TimingRec {
   int id;
@@ -60,6 +74,7 @@ struct fvo_ctx {
   std::string err;
   int kp_cap = 0;
   int64_t ws_bytes = 0;
+  std::vector<void*> allocs;          // every fvo_alloc of this context; freed by capi.cpp's release()
   // ORB workspace (per image b < max_batch)
   uint8_t* pyr = nullptr;     // [B][total_px]
   uint8_t* blur = nullptr;    // [B][total_px] debug only (orb_blur_debug), allocated on first use
@@ -150,14 +165,15 @@ hipEvent_t fvo_event(fvo_ctx* ctx);
     }                                                            \
   } while (0)
 
-// Per-module init/launchers (defined in the .hip files).
+// Per-module init/launchers (defined in the .hip files).  Arguments and fvo_config are validated by
+// capi.cpp before any of them runs; they call fvo_fail for HIP runtime errors only.
 int orb_init(fvo_ctx* ctx);
 int orb_run(fvo_ctx* ctx, const uint8_t* images, int batch, int64_t image_stride, int pitch, float* kp, uint8_t* desc,
             int32_t* counts, int cap, hipStream_t s);
 int bf_init(fvo_ctx* ctx);
 int bf_run(fvo_ctx* ctx, const uint8_t* q, const int32_t* nq, const uint8_t* t, const int32_t* nt, int batch, int cap,
            int32_t* matches, int32_t* nmatch, hipStream_t s);
-// k-nearest neighbours / ratio test (bf.hip); arguments validated by bf_api.cpp
+// k-nearest neighbours / ratio test (bf.hip)
 int bf_knn_run(fvo_ctx* ctx, const uint8_t* q, const int32_t* nq, const uint8_t* t, const int32_t* nt, int batch,
                int cap, int k, int32_t* knn, hipStream_t s);
 int bf_ratio_run(fvo_ctx* ctx, const uint8_t* q, const int32_t* nq, const uint8_t* t, const int32_t* nt, int batch,
@@ -169,6 +185,8 @@ int pose_init(fvo_ctx* ctx);
 int ransac_table_init(fvo_ctx* ctx);
 int orb_blur_debug(fvo_ctx* ctx);
 int orb_score_debug(fvo_ctx* ctx);
+int orb_retain_best_run(fvo_ctx* ctx, const float* keys, int n, int keep, int32_t* idx_out, int32_t* n_out,
+                         hipStream_t s);
 int backproject_run(fvo_ctx* ctx, const int16_t* disp, const float* kp0, const float* kp1, const int32_t* matches,
                     const int32_t* nmatch, int batch, int cap, const double* K, double baseline, float* P3, float* p2,
                     int32_t* npts, hipStream_t s);
@@ -192,9 +210,9 @@ int copy_regions_run(fvo_ctx* ctx, int count, const fvo_region* regions, hipStre
 int count_guard_run(fvo_ctx* ctx, const int32_t* cnt, const int32_t* q_cnt, int n, int sets, int32_t* status,
                     int32_t code, int32_t* nkp_out, hipStream_t s);
 int64_t voxel_workspace_bytes(int64_t n);
-int voxel_run(fvo_ctx* ctx, const double* pts, int64_t n, double voxel, void* ws, size_t ws_bytes, double* out,
+int voxel_run(fvo_ctx* ctx, const double* pts, int64_t n, double voxel, void* ws, double* out,
               int32_t* n_out, int32_t* status, hipStream_t s);
-// Speckle filter (speckle.hip); arguments validated by speckle_api.cpp.  ws: two int32 planes
+// Speckle filter (speckle.hip).  ws: two int32 planes
 // [batch][H*W] (fvo_speckle_workspace_bytes).
 int speckle_run(fvo_ctx* ctx, int16_t* disp, int batch, int H, int W, int64_t image_stride, int pitch, int new_val,
                 int max_speckle_size, int max_diff, void* ws, hipStream_t s);
@@ -225,6 +243,7 @@ int fvo_alloc(fvo_ctx* ctx, T** p, size_t n) {
   if (bytes == 0) bytes = 16;
   hipError_t e = hipMalloc((void**)p, bytes);
   if (e != hipSuccess) return fvo_fail(ctx, std::string("hipMalloc failed: ") + hipGetErrorString(e));
+  ctx->allocs.push_back(*p);
   ctx->ws_bytes += (int64_t)bytes;
   return 0;
 }

@@ -112,6 +112,7 @@ __global__ __launch_bounds__(256) void k_ing_undistort_gray(const uint8_t* __res
 
 int ingest_run(fvo_ctx* ctx, const uint8_t* bgr, int batch, int64_t sstride, int spitch, const double* K,
                const double* dist, uint8_t* gray, int64_t dstride, int dpitch, hipStream_t s) {
+  // arguments and config were validated by capi.cpp
   const int W = ctx->cfg.width, H = ctx->cfg.height;
   Lens L;
   for (int i = 0; i < 9; ++i) L.K[i] = K[i];
@@ -323,13 +324,11 @@ __global__ __launch_bounds__(256) void k_mb_blur(const uint8_t* __restrict__ src
 int motion_blur_run(fvo_ctx* ctx, const uint8_t* img, int batch, int64_t sstride, int spitch, int ksize,
                     const int32_t* centers, const int32_t* ncent, int cap, uint8_t* mask, uint8_t* out,
                     int64_t dstride, int dpitch, hipStream_t s) {
+  // arguments and config were validated by capi.cpp
   const int W = ctx->cfg.width, H = ctx->cfg.height;
   const int64_t mstride = (int64_t)W * H;
   const int half = ksize / 2;
   const bool seeds = cap > 0;
-  // k_mb_fix rewrites the mask a dword at a time: refuse a misaligned mask before any launch,
-  // so an error never leaves the mask in its intermediate (seed / dilated bit) encoding
-  if (seeds && (((uintptr_t)mask) & 3)) return fvo_fail(ctx, "motion blur: mask must be 4-byte aligned");
   if (seeds) {
     FVO_HIP(ctx, hipMemsetAsync(mask, 0, (size_t)mstride * batch, s));
     hipLaunchKernelGGL(k_mb_seed, dim3((cap + 255) / 256, batch), dim3(256), 0, s, centers, ncent, cap, mask, mstride,

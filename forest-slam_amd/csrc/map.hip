@@ -236,6 +236,7 @@ int vx_layout(int64_t n, VxLayout& L) {
 
 int map_transform_run(fvo_ctx* ctx, const float* pts, int stride, const int32_t* npts, int batch, int64_t cap,
                       const double* T, int32_t* count, int64_t map_cap, double* out64, float* out32, hipStream_t s) {
+  // arguments and config were validated by capi.cpp
   dim3 grid((unsigned)((cap + 255) / 256), batch);
   FVO_TIMED(ctx, KN_MAP_XFORM, s, {
     hipLaunchKernelGGL(k_map_xform, grid, dim3(256), 0, s, pts, stride, cap, npts, batch, T, count, map_cap, out64,
@@ -249,6 +250,7 @@ int map_transform_run(fvo_ctx* ctx, const float* pts, int stride, const int32_t*
 
 int chain_poses_run(fvo_ctx* ctx, const double* T, const int32_t* status, const int32_t* npts, int n_seq, int n,
                     double* cum, double* cum_out, int32_t* npts_out, hipStream_t s) {
+  // arguments and config were validated by capi.cpp
   hipLaunchKernelGGL(k_chain, dim3((n_seq + 3) / 4), dim3(64), 0, s, T, status, npts, n_seq, n, cum, cum_out,
                      npts_out);
   FVO_LAUNCH_CHECK(ctx);
@@ -261,11 +263,11 @@ int64_t voxel_workspace_bytes(int64_t n) {
   return (int64_t)L.total;
 }
 
-int voxel_run(fvo_ctx* ctx, const double* pts, int64_t n, double voxel, void* ws, size_t ws_bytes, double* out,
+int voxel_run(fvo_ctx* ctx, const double* pts, int64_t n, double voxel, void* ws, double* out,
               int32_t* n_out, int32_t* status, hipStream_t s) {
+  // arguments and config were validated by capi.cpp (the workspace size against voxel_workspace_bytes)
   VxLayout L;
-  if (vx_layout(n, L)) return fvo_fail(ctx, "voxel_down_sample: workspace size query failed");
-  if (ws_bytes < L.total) return fvo_fail(ctx, "voxel_down_sample: workspace too small");
+  if (vx_layout(n, L)) return fvo_fail(ctx, "voxel_down_sample: workspace size query failed");  // a hipcub error
   char* w = (char*)ws;
   uint64_t *ka = (uint64_t*)(w + L.keys_a), *kb = (uint64_t*)(w + L.keys_b);
   int32_t *ia = (int32_t*)(w + L.idx_a), *ib = (int32_t*)(w + L.idx_b);

@@ -1107,17 +1107,9 @@ OrbDev make_dev(const OrbGeom& g);
 }
 
 int orb_init(fvo_ctx* ctx) {
+  // arguments and config were validated by capi.cpp (check_orb_config)
   const fvo_config& c = ctx->cfg;
   OrbGeom& g = ctx->g;
-  if (c.nlevels < 1 || c.nlevels > FVO_MAX_LEVELS) return fvo_fail(ctx, "nlevels out of range");
-  if (c.first_level != 0 || c.wta_k != 2 || c.score_type != 0 || c.patch_size != 31)
-    return fvo_fail(ctx, "only firstLevel=0, WTA_K=2, HARRIS_SCORE, patchSize=31 are supported");
-  if (c.width > 4095 || c.height > 4095) return fvo_fail(ctx, "image dimensions must be < 4096");
-  // k_angle reads the whole 31x31 square around a keypoint unguarded; keypoints are kept
-  // edgeThreshold px inside the level, so it must cover the half patch (k_brief stages its
-  // rotated patch with REFLECT_101 and needs no such bound)
-  if (c.edge_threshold < c.patch_size / 2)
-    return fvo_fail(ctx, "edgeThreshold must be >= patchSize/2 (15)");
   g.nlevels = c.nlevels;
   const double sf = (double)c.scale_factor;
   int64_t off = 0, coff = 0;
@@ -1221,7 +1213,7 @@ int orb_init(fvo_ctx* ctx) {
       (rc = fvo_alloc(ctx, &ctx->koff, B * (c.nlevels + 1))) ||
       (rc = fvo_alloc(ctx, &ctx->scratch, B * c.nlevels * ctx->scratch_per)))
     return rc;
-  if ((g.w[0] + kTW - 1) / kTW > 64) return fvo_fail(ctx, "ORB: image wider than 4096 px");  // k_keep_compact: a lane per tile
+  // k_keep_compact: a lane per tile, at most 64 tiles across (width < 4096, check_orb_config)
   if ((rc = fvo_alloc(ctx, &ctx->fast_rec, B * make_dev(g).tile0[g.nlevels] * kTRec))) return rc;
   return 0;
 }
@@ -1258,6 +1250,7 @@ OrbDev make_dev(const OrbGeom& g) {
 
 int orb_run(fvo_ctx* ctx, const uint8_t* images, int batch, int64_t image_stride, int pitch, float* kp, uint8_t* desc,
             int32_t* counts, int cap, hipStream_t s) {
+  // arguments and config were validated by capi.cpp
   const fvo_config& c = ctx->cfg;
   const OrbGeom& g = ctx->g;
   const int L = g.nlevels;
@@ -1305,7 +1298,7 @@ int orb_run(fvo_ctx* ctx, const uint8_t* images, int batch, int64_t image_stride
 // Debug hook (fvo_debug_buffer 1): the blurred pyramid of the last fvo_orb_detect_compute
 // call, which the hot path no longer materialises (k_brief blurs each keypoint's patch).
 int orb_blur_debug(fvo_ctx* ctx) {
-  if (!ctx->pyr) return fvo_fail(ctx, "orb stage not enabled");
+  // arguments and config were validated by capi.cpp
   const OrbGeom& g = ctx->g;
   if (!ctx->blur) {
     int rc = fvo_alloc(ctx, &ctx->blur, (int64_t)ctx->cfg.max_batch * g.total_px);
@@ -1324,7 +1317,7 @@ int orb_blur_debug(fvo_ctx* ctx) {
 // Debug hook (fvo_debug_buffer 2): the FAST score map of the last call's pyramid, which the hot
 // path does not write (k_fast_nms keeps only the kept pixels' scores).
 int orb_score_debug(fvo_ctx* ctx) {
-  if (!ctx->pyr) return fvo_fail(ctx, "orb stage not enabled");
+  // arguments and config were validated by capi.cpp
   const OrbGeom& g = ctx->g;
   if (!ctx->score) {
     int rc = fvo_alloc(ctx, &ctx->score, (int64_t)ctx->cfg.max_batch * g.total_px);
@@ -1362,9 +1355,9 @@ __global__ __launch_bounds__(kSelThreads) void k_select_test(uint64_t* __restric
 
 // retainBest on n float keys (device memory); writes surviving original indices in
 // output order to idx_out and the count to *n_out.  Test hook for the selection stage.
-extern "C" int fvo_test_retain_best(fvo_ctx* ctx, const float* keys, int32_t n, int32_t keep, int32_t* idx_out,
-                                    int32_t* n_out, fvo_stream stream) {
-  hipStream_t s = (hipStream_t)stream;
+int orb_retain_best_run(fvo_ctx* ctx, const float* keys, int n, int keep, int32_t* idx_out, int32_t* n_out,
+                         hipStream_t s) {
+  // arguments and config were validated by capi.cpp
   uint64_t* a = nullptr;
   int32_t* scr = nullptr;
   FVO_HIP(ctx, hipMallocAsync((void**)&a, sizeof(uint64_t) * (size_t)std::max(n, 1), s));

@@ -1676,7 +1676,8 @@ __global__ __launch_bounds__(64, 2) void k_pnp_refine(const float* __restrict__ 
 }  // namespace
 
 int pose_init(fvo_ctx* ctx) {
-  ctx->pnp_max_iters = 1000;
+  // arguments and config were validated by capi.cpp
+  ctx->pnp_max_iters = kRansacMaxIters;
   const int64_t B = ctx->cfg.max_batch, n = B * ctx->kp_cap, it = B * ctx->pnp_max_iters;
   int rc;
   if ((rc = fvo_alloc(ctx, &ctx->pnp_sub, n)) || (rc = fvo_alloc(ctx, &ctx->pnp_hyp, 2 * n)) ||
@@ -1693,8 +1694,9 @@ int pose_init(fvo_ctx* ctx) {
 // The RNG(-1) subset table shared by PnP and the essential-matrix RANSAC (both draw 5-point
 // subsets with getSubset() from a fresh RNG(-1) per call): built once per context.
 int ransac_table_init(fvo_ctx* ctx) {
+  // arguments and config were validated by capi.cpp
   if (ctx->rs_table) return 0;
-  ctx->rs_table_iters = 1000;
+  ctx->rs_table_iters = kRansacMaxIters;
   int rc;
   if ((rc = fvo_alloc(ctx, &ctx->rs_table, (int64_t)(ctx->kp_cap + 1) * ctx->rs_table_iters * 5))) return rc;
   hipLaunchKernelGGL(k_pnp_table, dim3((ctx->kp_cap + 1 + 63) / 64), dim3(64), 0, 0, ctx->kp_cap,
@@ -1707,6 +1709,7 @@ int ransac_table_init(fvo_ctx* ctx) {
 int backproject_run(fvo_ctx* ctx, const int16_t* disp, const float* kp0, const float* kp1, const int32_t* matches,
                     const int32_t* nmatch, int batch, int cap, const double* K, double baseline, float* P3, float* p2,
                     int32_t* npts, hipStream_t s) {
+  // arguments and config were validated by capi.cpp
   CamF c{K[0], K[4], K[2], K[5], K[0] * baseline};
   FVO_TIMED(ctx, KN_BACKPROJECT, s, hipLaunchKernelGGL(k_backproject, dim3(batch), dim3(256), 0, s, disp, kp0, kp1,
                                                        matches, nmatch, ctx->cfg.width, ctx->cfg.height, cap, c, P3,
@@ -1718,7 +1721,7 @@ int backproject_run(fvo_ctx* ctx, const int16_t* disp, const float* kp0, const f
 int pnp_run(fvo_ctx* ctx, const float* P3, const float* p2, const int32_t* npts, int batch, int cap, const double* K,
             const double* dist, float reproj, double conf, int iters, double* rvec, double* tvec, double* T,
             int32_t* status, uint8_t* inliers, hipStream_t s) {
-  if (cap > ctx->kp_cap) return fvo_fail(ctx, "pnp: cap exceeds the context keypoint capacity");
+  // arguments and config were validated by capi.cpp
   Cam c{K[0], K[4], K[2], K[5], {dist[0], dist[1], dist[2], dist[3], dist[4]}};
   const float thr2 = (float)((double)reproj * reproj);
   const int maxIters = iters;

@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "fvo_device.h"
+#include "sgbm_params.h"
 
 namespace {
 
@@ -45,14 +46,8 @@ __device__ __forceinline__ u16x2 vmin(u16x2 a, u16x2 b) { return __builtin_eleme
 __device__ __forceinline__ u16x2 splat(uint32_t s) { return as_v((s & 0xFFFFu) | (s << 16)); }
 // (m + P2) in both halves for a path minimum m: one v_mad_u32_u24 (m * 0x10001 + P2 * 0x10001)
 // instead of add + shift + and_or.  Exact: m <= 49 x the largest pixel cost + P2, so m + P2 <
-// 3 (49 (2 ftzero + 63) + P2) <= 0xFFFF (sgbm_init) and no carry crosses the halves.
+// 3 (49 (2 ftzero + 63) + P2) <= 0xFFFF (check_sgbm_config) and no carry crosses the halves.
 __device__ __forceinline__ u16x2 splat_p2(uint32_t m, uint32_t P2) { return as_v(__umul24(m, 0x10001u) + P2 * 0x10001u); }
-
-struct SgParams {
-  int W, H, D, minD, minX1, width1, P1, P2, ftzero, disp12, ss, ov, nstripes;
-  int HG;   // row groups of 16
-  int HG4;  // row groups of 4 (volume layout)
-};
 
 constexpr uint32_t kSent = 0x7FFFu;  // "no neighbour" entry: P1 + 0x7FFF never wins the min
 
@@ -200,7 +195,7 @@ __host__ __device__ constexpr int sg_ring_raw(int D) { return sg_pow2(D + 16); }
 //   c + min(A, mp + P2) - mp  ==  min((A + c) - mp, c + P2),  A = min(min(dm, dp) + P1, cur)
 // exact, not only modulo 2^16: A >= mp (every term is a state entry of the previous column or
 // a sentinel, and mp is their minimum), and A + c <= Lmax + Cmax <= 2 Cmax + P2 < 0xFFFF by
-// sgbm_init's bound (Cmax = 49 (2 ftzero + 63)), so neither side wraps and the min compares
+// the config bound (Cmax = 49 (2 ftzero + 63)), so neither side wraps and the min compares
 // true values; min(dm + P1, dp + P1) = min(dm, dp) + P1 (no path value + P1 wraps, by the same
 // bound).  A + c and c + P2 do not depend on mp.  The row minimum: the packed minimum of
 // the words, its halves swapped and min-ed (both halves then hold it), four DPP steps as u32
@@ -1187,43 +1182,10 @@ __global__ void k_sg_prep(uint32_t* ctl, int nb) {
   for (int b = t; b < nb; b += blockDim.x) ctl[4 + b] = 0;
 }
 
-// Schedules and launch shapes (fvo_config, validated by sgbm_init; every variant is
-// bit-identical and parity-tested), sgbm_mode:
-//   FVO_SGBM_CLASSIC  one cost pass, one row pass running both sweeps, with sgbm_lanes lanes per
-//                     column (4, 8 or 16) and sgbm_cols columns per block (4: 32/64; 8: 16/32; 16: 32)
-//   FVO_SGBM_LPATH    the L path in the cost pass, handed from column block to column block: one V
-//                     read per pair fewer (<= 300 MB/pair) but slower -- DESIGN.md §4.2 r5
-int sg_lanes(const fvo_config& c) { return c.sgbm_lanes > 0 ? c.sgbm_lanes : 8; }
-int sg_cols(const fvo_config& c) { return c.sgbm_cols > 0 ? c.sgbm_cols : (sg_lanes(c) == 4 ? 64 : 32); }
-
-SgParams make_params(const fvo_config& c) {
-  SgParams p;
-  p.W = c.width;
-  p.H = c.height;
-  p.D = c.num_disparities;
-  p.minD = c.min_disparity;
-  int maxD = p.minD + p.D;
-  p.minX1 = maxD > 0 ? maxD : 0;
-  int maxX1 = c.width + (p.minD < 0 ? p.minD : 0);
-  p.width1 = maxX1 - p.minX1;
-  p.P1 = c.P1 > 0 ? c.P1 : 2;
-  p.P2 = std::max(c.P2 > 0 ? c.P2 : 5, p.P1 + 1);
-  p.ftzero = std::max(c.pre_filter_cap, 15) | 1;
-  p.disp12 = c.disp12_max_diff > 0 ? c.disp12_max_diff : 1;
-  p.nstripes = c.sgbm_stripes;
-  p.ss = (int)std::ceil(c.height / (double)p.nstripes);
-  p.ov = (c.block_size / 2 + 1) + (int)std::ceil(0.1 * p.ss);
-  p.HG = (c.height + 15) / 16;
-  p.HG4 = (c.height + 3) / 4;
-  return p;
-}
-
 // Checkpoints of the left->right path (per 4-row block or per row): at x = W1-9-8s, s < nck.
 int sg_nck(const SgParams& p) { return p.width1 / 8 + 2; }  // + a dummy slot
 int sg_ckw(int D) { return D / 32 + 1 <= 4 ? 4 : 8; }
 int sg_nblk(const SgParams& p) { return (p.H + 3) / 4; }
-constexpr int kSgCB = 32;  // columns per cost block of the L-path schedule
-int sg_nk(const SgParams& p) { return (p.width1 + kSgCB - 1) / kSgCB; }
 
 template <int D>
 void launch_sgbm(fvo_ctx* ctx, const SgParams& p, const uint8_t* L, const uint8_t* R, int nb, int64_t stride,
@@ -1234,7 +1196,7 @@ void launch_sgbm(fvo_ctx* ctx, const SgParams& p, const uint8_t* L, const uint8_
   const int16_t invalid = (int16_t)((p.minD - 1) * 16);
   const fvo_config& cfg = ctx->cfg;
   if (cfg.sgbm_mode == FVO_SGBM_CLASSIC) {
-    // (G, CB) of the cost pass, validated by sgbm_init; the grid follows the kernel launched
+    // (G, CB) of the cost pass, validated by check_sgbm_config; the grid follows the kernel launched
     const int g = sg_lanes(cfg), cbr = sg_cols(cfg);
     typedef void (*CostKernel)(const uint8_t*, const uint8_t*, int64_t, int, SgParams, uint16_t*, uint16_t*, SgLink);
     CostKernel kern;
@@ -1269,33 +1231,9 @@ void launch_sgbm(fvo_ctx* ctx, const SgParams& p, const uint8_t* L, const uint8_
 }  // namespace
 
 int sgbm_init(fvo_ctx* ctx) {
+  // arguments and config were validated by capi.cpp (check_sgbm_config)
   const fvo_config& c = ctx->cfg;
-  if (c.block_size != 7) return fvo_fail(ctx, "SGBM: only blockSize=7 is supported");
-  if (c.num_disparities != 64 && c.num_disparities != 96 && c.num_disparities != 128)
-    return fvo_fail(ctx, "SGBM: numDisparities must be 64, 96 or 128");
-  if (c.uniqueness_ratio != 0) return fvo_fail(ctx, "SGBM: only uniquenessRatio=0 is supported");
-  if (c.sgbm_stripes < 1) return fvo_fail(ctx, "SGBM: stripes must be >= 1");
-  if (c.sgbm_mode != FVO_SGBM_CLASSIC && c.sgbm_mode != FVO_SGBM_LPATH)
-    return fvo_fail(ctx, "SGBM: sgbm_mode must be FVO_SGBM_CLASSIC or FVO_SGBM_LPATH");
-  if (c.sgbm_mode == FVO_SGBM_CLASSIC) {
-    const int g = sg_lanes(c), cb = sg_cols(c);
-    if (!((g == 4 && (cb == 32 || cb == 64)) || (g == 8 && (cb == 16 || cb == 32)) || (g == 16 && cb == 32)))
-      return fvo_fail(ctx, "SGBM: (sgbm_lanes, sgbm_cols) must be (4, 32|64), (8, 16|32) or (16, 32)");
-  } else if (c.sgbm_lanes != 0 || c.sgbm_cols != 0) {
-    return fvo_fail(ctx, "SGBM: sgbm_lanes / sgbm_cols apply to the classic schedule only (leave them 0)");
-  }
-  if (c.sgbm_handoff_us < -1) return fvo_fail(ctx, "SGBM: sgbm_handoff_us must be >= -1");
   SgParams p = make_params(c);
-  if (p.width1 <= 0) return fvo_fail(ctx, "SGBM: image narrower than numDisparities");
-  // path values are at most C + P2 with C <= 49 x the largest BT pixel cost (2 ftzero + 255/4);
-  // the kernels add P1 to them in u16 (min(a, b) + P1 for min(a + P1, b + P1)), so that sum
-  // must not wrap -- OpenCV's 16-bit CostType carries the same assumption
-  if (49 * (2 * p.ftzero + 63) + p.P2 + p.P1 > 0xFFFF)
-    return fvo_fail(ctx, "SGBM: P1/P2/preFilterCap too large for 16-bit path costs");
-  // the row pass sums S = L + R + V in u16 lanes and its WTA keys on S: each path is at most
-  // C + P2, so 3 (C + P2) must not wrap either
-  if (3 * (49 * (2 * p.ftzero + 63) + p.P2) > 0xFFFF)
-    return fvo_fail(ctx, "SGBM: P2/preFilterCap too large for the 16-bit aggregated cost");
   const int64_t B = c.sgbm_max_batch > 0 ? std::min(c.sgbm_max_batch, c.max_batch) : c.max_batch;
   const int64_t plane = (int64_t)p.width1 * p.D;
   int rc;
@@ -1308,9 +1246,6 @@ int sgbm_init(fvo_ctx* ctx) {
   // sg_hand: the L path's hand-off granules [B][H][2][D/32][16] u64; sg_ctl: ticket, generation,
   // timeout count, per-pair failure flags.  Both zeroed once (tags of a zeroed granule never match)
   const int64_t hand = (int64_t)p.H * 2 * (p.D / 32) * 16;
-  // the L path's hand-off tags carry the column block in 7 bits
-  if (c.sgbm_mode == FVO_SGBM_LPATH && sg_nk(p) >= 128)
-    return fvo_fail(ctx, "SGBM: FVO_SGBM_LPATH needs width - numDisparities <= 4064 (use the classic schedule)");
   // sg_M: min over d of every stored V row, [B][HG4 + nstripes][width1][4] u16
   if ((rc = fvo_alloc(ctx, &ctx->sg_V, B * vol)) || (rc = fvo_alloc(ctx, &ctx->sg_M, B * vol / p.D)) ||
       (rc = fvo_alloc(ctx, &ctx->sg_ckpt, B * ckp)) ||
@@ -1324,6 +1259,7 @@ int sgbm_init(fvo_ctx* ctx) {
 
 int sgbm_run(fvo_ctx* ctx, const uint8_t* L, const uint8_t* R, int batch, int64_t image_stride, int pitch,
              int16_t* disp, int32_t* status, hipStream_t s) {
+  // arguments and config were validated by capi.cpp
   SgParams p = make_params(ctx->cfg);
   switch (p.D) {
     case 64: launch_sgbm<64>(ctx, p, L, R, batch, image_stride, pitch, disp, status, s); break;

@@ -223,6 +223,7 @@ __global__ __launch_bounds__(256) void k_spk_apply(int16_t* __restrict__ disp, i
 
 int speckle_run(fvo_ctx* ctx, int16_t* disp, int batch, int H, int W, int64_t istride, int pitch, int newval,
                 int maxsize, int maxdiff, void* ws, hipStream_t s) {
+  // arguments and config were validated by capi.cpp
   const int64_t hw = (int64_t)H * W;
   const int maxd = maxdiff > 65535 ? 65535 : maxdiff;  // int16 values differ by at most 65535
   const int ntx = (W + kSpkTW - 1) / kSpkTW, nty = (H + kSpkTH - 1) / kSpkTH;

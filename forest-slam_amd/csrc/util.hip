@@ -47,6 +47,7 @@ __global__ void k_count_guard(const int32_t* __restrict__ cnt, const int32_t* __
 }  // namespace
 
 int copy_regions_run(fvo_ctx* ctx, int count, const fvo_region* regions, hipStream_t s) {
+  // arguments and config were validated by capi.cpp
   FvoRegions r{};
   int64_t most = 0;
   for (int i = 0; i < count; ++i) {
@@ -62,6 +63,7 @@ int copy_regions_run(fvo_ctx* ctx, int count, const fvo_region* regions, hipStre
 
 int count_guard_run(fvo_ctx* ctx, const int32_t* cnt, const int32_t* q_cnt, int n, int sets, int32_t* status,
                     int32_t code, int32_t* nkp_out, hipStream_t s) {
+  // arguments and config were validated by capi.cpp
   hipLaunchKernelGGL(k_count_guard, dim3((n + 63) / 64), dim3(64), 0, s, cnt, q_cnt, n, sets, status, code, nkp_out);
   FVO_LAUNCH_CHECK(ctx);
   return 0;

@@ -409,6 +409,9 @@ int fvo_timing_read(fvo_ctx* ctx, double* ms, int32_t* launches);
  * iteration, points, 9 the SGBM control words: u32 ticket, generation, L-path hand-off timeouts
  * (must stay 0), reserved, then one failure flag per pair).  For stage-by-stage parity tests only. */
 int fvo_debug_buffer(fvo_ctx* ctx, int which, void** ptr, int64_t* bytes);
+/* The first `bytes` bytes (<= the size fvo_debug_buffer reports) of that buffer copied to host
+ * memory, after synchronising the context's device.  A HIP error is reported by fvo_last_error. */
+int fvo_debug_copy(fvo_ctx* ctx, int which, void* host_dst, int64_t bytes);
 
 #ifdef __cplusplus
 }

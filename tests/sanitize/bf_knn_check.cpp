@@ -1,41 +1,17 @@
 // Argument validation of the k-nearest-neighbour matcher's and the ratio test's C ABI
-// (csrc/bf_api.cpp) exercised on the host under AddressSanitizer + UndefinedBehaviorSanitizer.
-// Linked with csrc/capi.cpp and tests/sanitize/host_stubs.cpp (context lifetime, fvo_fail) and
-// its own stubs of the launchers bf_knn_run / bf_ratio_run, which record what the entry points
-// passed on.  Built and run by tests/test_bf_knn.py.  Exit status 0 = all checks passed.
+// (csrc/capi.cpp) exercised on the host under AddressSanitizer + UndefinedBehaviorSanitizer.
+// Linked with csrc/capi.cpp and tests/sanitize/host_stubs.cpp, whose stubs of the launchers
+// bf_knn_run / bf_ratio_run record what the entry points passed on (g_bf).  Built and run by
+// tests/test_bf_knn.py.  Exit status 0 = all checks passed.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <limits>
 
-#include "../../forest-slam_amd/csrc/fvo_internal.h"
+#include "host_stubs.h"
 
-static int g_fail = 0, g_checks = 0, g_launches = 0;
-static struct {
-  int batch, cap, k, mutual;
-  double ratio;
-  const void *q, *t, *out;
-} g_args;
-
-int bf_knn_run(fvo_ctx*, const uint8_t* q, const int32_t* nq, const uint8_t* t, const int32_t* nt, int batch, int cap,
-               int k, int32_t* knn, hipStream_t) {
-  ++g_launches;
-  g_args = {batch, cap, k, -1, 0.0, q, t, knn};
-  // first / last element of every buffer as the entry point sized them
-  knn[((int64_t)batch * cap * k - 1) * 2 + 1] = q[(int64_t)batch * cap * 32 - 1] + t[(int64_t)batch * cap * 32 - 1];
-  knn[0] = nq[batch - 1] + nt[batch - 1] + q[0] + t[0];
-  return 0;
-}
-
-int bf_ratio_run(fvo_ctx*, const uint8_t* q, const int32_t* nq, const uint8_t* t, const int32_t* nt, int batch,
-                 int cap, double ratio, int mutual, int32_t* matches, int32_t* nmatch, hipStream_t) {
-  ++g_launches;
-  g_args = {batch, cap, 2, mutual, ratio, q, t, matches};
-  matches[(int64_t)batch * cap * 3 - 1] = q[(int64_t)batch * cap * 32 - 1] + t[(int64_t)batch * cap * 32 - 1];
-  nmatch[batch - 1] = nq[batch - 1] + nt[batch - 1];
-  return 0;
-}
+static int g_fail = 0, g_checks = 0;
 
 #define CHECK(cond)                                                       \
   do {                                                                    \
@@ -76,8 +52,8 @@ int main() {
   for (int k = 1; k <= FVO_BF_MAX_K; ++k) {
     g_launches = 0;
     CHECK(fvo_bf_knn_match(c, q, nq, t, nt, B, CAP, k, knn, nullptr) == 0);
-    CHECK(g_launches == 1 && g_args.batch == B && g_args.cap == CAP && g_args.k == k && g_args.q == q &&
-          g_args.t == t && g_args.out == knn);
+    CHECK(g_launches == 1 && g_bf.batch == B && g_bf.cap == CAP && g_bf.k == k && g_bf.q == q &&
+          g_bf.t == t && g_bf.out == knn);
   }
   g_launches = 0;
   CHECK(fvo_bf_knn_match(c, q + 16, nq, t + 16, nt, 1, 1, 1, knn, nullptr) == 0);  // 16-byte aligned is enough
@@ -112,12 +88,12 @@ int main() {
   // ---- ratio: good calls
   g_launches = 0;
   CHECK(fvo_bf_ratio_match(c, q, nq, t, nt, B, CAP, 0.75, 1, matches, nm, nullptr) == 0);
-  CHECK(g_launches == 1 && g_args.batch == B && g_args.cap == CAP && g_args.ratio == 0.75 && g_args.mutual == 1 &&
-        g_args.q == q && g_args.t == t && g_args.out == matches && nm[B - 1] == 9);
+  CHECK(g_launches == 1 && g_bf.batch == B && g_bf.cap == CAP && g_bf.ratio == 0.75 && g_bf.mutual == 1 &&
+        g_bf.q == q && g_bf.t == t && g_bf.out == matches && nm[B - 1] == 9);
   CHECK(fvo_bf_ratio_match(c, q, nq, t, nt, 1, 1, 1e-300, 0, matches, nm, nullptr) == 0);
-  CHECK(g_args.mutual == 0 && g_args.ratio == 1e-300);
+  CHECK(g_bf.mutual == 0 && g_bf.ratio == 1e-300);
   CHECK(fvo_bf_ratio_match(c, q, nq, t, nt, 2, CAP, 1e300, -7, matches, nm, nullptr) == 0);  // any non-zero = mutual
-  CHECK(g_args.mutual == 1 && g_launches == 3);
+  CHECK(g_bf.mutual == 1 && g_launches == 3);
   // refusals
   g_launches = 0;
   CHECK(fvo_bf_ratio_match(nullptr, q, nq, t, nt, B, CAP, 0.75, 1, matches, nm, nullptr) < 0);

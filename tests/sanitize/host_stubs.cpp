@@ -1,29 +1,51 @@
-// Host-only test double of libfvo's device layer, for the sanitizer build of capi.cpp
-// (tools/sanitize.sh): the per-stage init / launch functions and the few HIP runtime calls
-// capi.cpp makes are replaced by functions that record which launcher the entry point reached
-// and touch every pointer argument's first element on the host side where it is host memory
-// in this test (nothing here runs on a GPU).  Test infrastructure only; never linked into
-// libfvo.so.
-#include <cstring>
-#include <string>
+// Host-only test double of libfvo's device layer, for the sanitizer programs of this directory
+// (capi.cpp + this file + one check program): the per-stage init / launch functions and the few
+// HIP runtime calls capi.cpp makes are replaced by functions that record what the entry point
+// reached (host_stubs.h).  The inits only allocate, through fvo_alloc and the hipMalloc stub, so
+// capi.cpp's own release path frees them; no check or limit of the product is restated here.
+// Nothing runs on a GPU.  Test infrastructure only; never linked into libfvo.so.
+#include "host_stubs.h"
 
-#include "../../forest-slam_amd/csrc/fvo_internal.h"
+#include <cstring>
 
 std::string g_last_launch;
+int g_launches = 0, g_live_allocs = 0;
+hipError_t g_memcpy_result = hipSuccess;
+BfArgs g_bf;
+SpeckleArgs g_spk;
 static int g_fake_event = 0;
 
 static int hit(const char* name) {
   g_last_launch = name;
+  ++g_launches;
   return 0;
 }
 
-// --- HIP runtime calls made by capi.cpp
+// one small allocation the context owns, and the init's name
+template <typename T>
+static int init(fvo_ctx* c, T** field, const char* name, size_t n = 16) {
+  g_last_launch = name;
+  return fvo_alloc(c, field, n);
+}
+
+// --- HIP runtime calls made by capi.cpp and fvo_alloc
 extern "C" {
 hipError_t hipSetDevice(int d) { return d >= 0 && d < 8 ? hipSuccess : hipErrorInvalidDevice; }
-hipError_t hipFree(void* p) {
-  delete[] static_cast<char*>(p);
+hipError_t hipMalloc(void** p, size_t n) {
+  *p = new char[n]();
+  ++g_live_allocs;
   return hipSuccess;
 }
+hipError_t hipFree(void* p) {
+  delete[] static_cast<char*>(p);
+  --g_live_allocs;
+  return hipSuccess;
+}
+hipError_t hipMemcpy(void* dst, const void* src, size_t n, hipMemcpyKind) {
+  if (g_memcpy_result == hipSuccess) std::memcpy(dst, src, n);
+  return g_memcpy_result;
+}
+hipError_t hipDeviceSynchronize(void) { return hipSuccess; }
 hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
 hipError_t hipEventCreate(hipEvent_t* e) {
   *e = reinterpret_cast<hipEvent_t>(&g_fake_event);
@@ -39,17 +61,13 @@ hipError_t hipMemsetAsync(void*, int, size_t, hipStream_t) { return hipSuccess; 
 const char* hipGetErrorString(hipError_t) { return "stub hip error"; }
 }
 
-// --- stage inits: one small host allocation each, released by capi.cpp's hipFree
-int orb_init(fvo_ctx* c) { c->pyr = reinterpret_cast<uint8_t*>(new char[16]); return hit("orb_init"); }
-int bf_init(fvo_ctx* c) { c->bf_rowkey = reinterpret_cast<uint32_t*>(new char[16]); return hit("bf_init"); }
-int sgbm_init(fvo_ctx* c) {
-  if (c->cfg.block_size != 7) return fvo_fail(c, "SGBM: only blockSize=7 is supported");
-  c->sg_raw = reinterpret_cast<int16_t*>(new char[16]);
-  return hit("sgbm_init");
-}
-int pose_init(fvo_ctx* c) { c->pnp_max_iters = 1000; return hit("pose_init"); }
-int ba_init(fvo_ctx*) { return hit("ba_init"); }
-int mono_init(fvo_ctx*) { return hit("mono_init"); }
+// --- stage inits
+int orb_init(fvo_ctx* c) { return init(c, &c->pyr, "orb_init"); }
+int bf_init(fvo_ctx* c) { return init(c, &c->bf_rowkey, "bf_init"); }
+int sgbm_init(fvo_ctx* c) { return init(c, &c->sg_ctl, "sgbm_init", 4 + c->cfg.max_batch); }  // debug buffer 9
+int pose_init(fvo_ctx* c) { return init(c, &c->pnp_good, "pose_init"); }
+int ba_init(fvo_ctx* c) { return init(c, reinterpret_cast<char**>(&c->ba_ws), "ba_init"); }
+int mono_init(fvo_ctx* c) { return init(c, &c->em_x, "mono_init"); }
 
 // --- launchers
 int orb_run(fvo_ctx*, const uint8_t*, int, int64_t, int, float*, uint8_t*, int32_t*, int, hipStream_t) {
@@ -58,6 +76,27 @@ int orb_run(fvo_ctx*, const uint8_t*, int, int64_t, int, float*, uint8_t*, int32
 int bf_run(fvo_ctx*, const uint8_t*, const int32_t*, const uint8_t*, const int32_t*, int, int, int32_t*, int32_t*,
            hipStream_t) {
   return hit("bf_run");
+}
+// (the three below also touch the first / last element of every buffer as the entry point sized them)
+int bf_knn_run(fvo_ctx*, const uint8_t* q, const int32_t* nq, const uint8_t* t, const int32_t* nt, int batch, int cap,
+               int k, int32_t* knn, hipStream_t) {
+  g_bf = {batch, cap, k, -1, 0.0, q, t, knn};
+  knn[((int64_t)batch * cap * k - 1) * 2 + 1] = q[(int64_t)batch * cap * 32 - 1] + t[(int64_t)batch * cap * 32 - 1];
+  knn[0] = nq[batch - 1] + nt[batch - 1] + q[0] + t[0];
+  return hit("bf_knn_run");
+}
+int bf_ratio_run(fvo_ctx*, const uint8_t* q, const int32_t* nq, const uint8_t* t, const int32_t* nt, int batch,
+                 int cap, double ratio, int mutual, int32_t* matches, int32_t* nmatch, hipStream_t) {
+  g_bf = {batch, cap, 2, mutual, ratio, q, t, matches};
+  matches[(int64_t)batch * cap * 3 - 1] = q[(int64_t)batch * cap * 32 - 1] + t[(int64_t)batch * cap * 32 - 1];
+  nmatch[batch - 1] = nq[batch - 1] + nt[batch - 1];
+  return hit("bf_ratio_run");
+}
+int speckle_run(fvo_ctx*, int16_t* disp, int batch, int H, int W, int64_t image_stride, int pitch, int new_val,
+                int max_speckle_size, int max_diff, void* ws, hipStream_t) {
+  g_spk = {batch, H, W, pitch, new_val, max_speckle_size, max_diff, image_stride, ws};
+  disp[0] = disp[(int64_t)(batch - 1) * image_stride + (int64_t)(H - 1) * pitch + W - 1];
+  return hit("speckle_run");
 }
 int sgbm_run(fvo_ctx*, const uint8_t*, const uint8_t*, int, int64_t, int, int16_t*, int32_t*, hipStream_t) {
   return hit("sgbm_run");
@@ -115,8 +154,11 @@ int count_guard_run(fvo_ctx*, const int32_t*, const int32_t*, int, int, int32_t*
   return hit("count_guard_run");
 }
 int64_t voxel_workspace_bytes(int64_t n) { return 64 * n + 4096; }
-int voxel_run(fvo_ctx*, const double*, int64_t, double, void*, size_t, double*, int32_t*, int32_t*, hipStream_t) {
+int voxel_run(fvo_ctx*, const double*, int64_t, double, void*, double*, int32_t*, int32_t*, hipStream_t) {
   return hit("voxel_run");
 }
 int orb_blur_debug(fvo_ctx*) { return hit("orb_blur_debug"); }
 int orb_score_debug(fvo_ctx*) { return hit("orb_score_debug"); }
+int orb_retain_best_run(fvo_ctx*, const float*, int, int, int32_t*, int32_t*, hipStream_t) {
+  return hit("orb_retain_best_run");
+}

@@ -1,0 +1,25 @@
+// What tests/sanitize/host_stubs.cpp records for the check programs to read.
+#pragma once
+
+#include <string>
+
+#include "../../forest-slam_amd/csrc/fvo_internal.h"
+
+extern std::string g_last_launch;   // name of the init or launcher reached last
+extern int g_launches;              // launcher calls (inits not counted)
+extern int g_live_allocs;           // hipMalloc calls not yet matched by a hipFree
+extern hipError_t g_memcpy_result;  // what the hipMemcpy stub answers (hipSuccess: it copies)
+
+// the arguments bf_knn_run / bf_ratio_run and speckle_run were last called with
+struct BfArgs {
+  int batch, cap, k, mutual;
+  double ratio;
+  const void *q, *t, *out;
+};
+struct SpeckleArgs {
+  int batch, H, W, pitch, new_val, max_size, max_diff;
+  int64_t stride;
+  void* ws;
+};
+extern BfArgs g_bf;
+extern SpeckleArgs g_spk;

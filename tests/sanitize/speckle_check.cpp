@@ -1,28 +1,15 @@
 // Argument validation and workspace arithmetic of the speckle filter's C ABI
-// (csrc/speckle_api.cpp) exercised on the host under AddressSanitizer + UndefinedBehaviorSanitizer.
-// Linked with csrc/capi.cpp and tests/sanitize/host_stubs.cpp (context lifetime, fvo_fail) and
-// its own stub of the launcher speckle_run, which records what the entry point passed on.
-// Built and run by tests/test_speckle.py.  Exit status 0 = all checks passed.
+// (csrc/capi.cpp) exercised on the host under AddressSanitizer + UndefinedBehaviorSanitizer.
+// Linked with csrc/capi.cpp and tests/sanitize/host_stubs.cpp, whose stub of the launcher
+// speckle_run records what the entry point passed on (g_spk).  Built and run by
+// tests/test_speckle.py.  Exit status 0 = all checks passed.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 
-#include "../../forest-slam_amd/csrc/fvo_internal.h"
+#include "host_stubs.h"
 
-static int g_fail = 0, g_checks = 0, g_launches = 0;
-static struct {
-  int batch, H, W, pitch, new_val, max_size, max_diff;
-  int64_t stride;
-  void* ws;
-} g_args;
-
-int speckle_run(fvo_ctx*, int16_t* disp, int batch, int H, int W, int64_t image_stride, int pitch, int new_val,
-                int max_speckle_size, int max_diff, void* ws, hipStream_t) {
-  ++g_launches;
-  g_args = {batch, H, W, pitch, new_val, max_speckle_size, max_diff, image_stride, ws};
-  disp[0] = disp[(int64_t)(batch - 1) * image_stride + (int64_t)(H - 1) * pitch + W - 1];  // first / last pixel
-  return 0;
-}
+static int g_fail = 0, g_checks = 0;
 
 #define CHECK(cond)                                                       \
   do {                                                                    \
@@ -85,8 +72,8 @@ int main() {
   // good call: the launcher is reached with the arguments as given
   CHECK(fvo_filter_speckles(c, disp, 3, 5, 12, 5 * 16, 16, -16, 100, 32, ws, need, nullptr) == 0);
   CHECK(g_launches == 1);
-  CHECK(g_args.batch == 3 && g_args.H == 5 && g_args.W == 12 && g_args.stride == 80 && g_args.pitch == 16 &&
-        g_args.new_val == -16 && g_args.max_size == 100 && g_args.max_diff == 32 && g_args.ws == ws);
+  CHECK(g_spk.batch == 3 && g_spk.H == 5 && g_spk.W == 12 && g_spk.stride == 80 && g_spk.pitch == 16 &&
+        g_spk.new_val == -16 && g_spk.max_size == 100 && g_spk.max_diff == 32 && g_spk.ws == ws);
   // int16 extremes of new_val, max_diff 0, a larger workspace, any image size (not the context's)
   g_launches = 0;
   CHECK(fvo_filter_speckles(c, disp, 1, 5, 12, 80, 16, -32768, 1, 0, ws, need + 1, nullptr) == 0);

@@ -7,6 +7,7 @@ import re
 import pytest
 
 from conftest import ROOT, gpu_available
+from sanitize_build import run_check
 
 
 def _declared():
@@ -105,3 +106,10 @@ def test_integration_raw_binding_snippet_runs_to_create():
         assert ns["rc"] == 0
     else:
         assert ns["rc"] < 0 and not ns["ctx"].value
+
+
+def test_boundary_checks_under_sanitizers(tmp_path):
+    """Every config and argument refusal of csrc/capi.cpp by its exact message, the accepted bound
+    next to each, context lifetime (nothing left allocated) and fvo_debug_copy, as a stand-alone
+    ASan + UBSan program: tests/sanitize/capi_check.cpp."""
+    run_check("capi_check", tmp_path)

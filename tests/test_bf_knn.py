@@ -4,15 +4,13 @@ match_ratio, against the NumPy restatement tests/bf_knn_ref.py.  Distances are i
 ratio decision is one IEEE multiply and compare, so every GPU comparison is exact."""
 import ctypes
 import functools
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import bf_knn_ref as ref
-from conftest import ROOT, gpu_available
+from conftest import gpu_available
+from sanitize_build import run_check
 
 
 def _desc(rows):
@@ -221,36 +219,10 @@ def test_shim_without_gpu_raises():
 
 
 def test_host_validation_under_sanitizers(tmp_path):
-    """csrc/bf_api.cpp (every refusal, the k bound, null pointers, cap overflow, the no-launch
-    case) as a stand-alone ASan + UBSan program: tests/sanitize/bf_knn_check.cpp."""
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    # as tests/test_speckle.py: the runtimes are linked into the program itself, unless this
-    # process already runs under a shared ASan runtime (two runtimes refuse to start)
-    shared = hasattr(ctypes.CDLL(None), "__asan_init")
-    rt = subprocess.run([gxx, "-print-file-name=" + ("libasan.so" if shared else "libasan.a")], capture_output=True,
-                        text=True).stdout.strip()
-    if not os.path.isabs(rt) or not os.path.exists(rt):
-        pytest.skip("the ASan runtime of g++ is not installed")
-    link = [] if shared else ["-static-libasan", "-static-libubsan"]
-    hip_inc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
-    if not os.path.exists(os.path.join(hip_inc, "hip", "hip_runtime.h")):
-        pytest.skip("HIP headers not found")
-    exe = str(tmp_path / "bf_knn_check")
-    csrc = os.path.join(ROOT, "forest-slam_amd", "csrc")
-    san = os.path.join(ROOT, "tests", "sanitize")
-    cmd = [gxx, "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", "-g", "-O1", "-D__HIP_PLATFORM_AMD__", "-I", hip_inc,
-           "-I", os.path.join(ROOT, "include"), os.path.join(csrc, "capi.cpp"), os.path.join(csrc, "bf_api.cpp"),
-           os.path.join(san, "host_stubs.cpp"), os.path.join(san, "bf_knn_check.cpp"), "-o", exe] + link
-    b = subprocess.run(cmd, capture_output=True, text=True)
-    assert b.returncode == 0, b.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([exe], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
-    assert "0 failed" in r.stdout
+    """fvo_bf_knn_match and fvo_bf_ratio_match of csrc/capi.cpp (every refusal, the k bound, null
+    pointers, cap overflow, the no-launch case) as a stand-alone ASan + UBSan program:
+    tests/sanitize/bf_knn_check.cpp."""
+    run_check("bf_knn_check", tmp_path)
 
 
 # ----------------------------------------------------------------------------- GPU

@@ -2,15 +2,13 @@
 the cv2 shim and the stereo front end, against the flood-fill restatement tests/speckle_ref.py.
 A region's size is a fact about the image, so every GPU comparison is exact (np.array_equal)."""
 import functools
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import speckle_ref as ref
-from conftest import ROOT, gpu_available
+from conftest import gpu_available
+from sanitize_build import run_check
 
 NV = -16  # (minDisparity - 1) * 16 of the reference's StereoSGBM
 
@@ -124,39 +122,10 @@ def test_sgbm_with_speckle_arguments_matches_opencv():
 
 
 def test_host_validation_under_sanitizers(tmp_path):
-    """csrc/speckle_api.cpp (every error path, the no-launch cases, the workspace arithmetic)
-    as a stand-alone ASan + UBSan program: tests/sanitize/speckle_check.cpp."""
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    # The sanitizer runtimes are linked into the program itself, so it checks every allocation
-    # whatever else the environment loads into processes.  Only when this Python process already
-    # runs under an ASan runtime (tools/sanitize.sh leg 3, inherited by children) the program
-    # links against that shared runtime instead: two runtimes in one process refuse to start.
-    import ctypes
-    shared = hasattr(ctypes.CDLL(None), "__asan_init")
-    rt = subprocess.run([gxx, "-print-file-name=" + ("libasan.so" if shared else "libasan.a")], capture_output=True,
-                        text=True).stdout.strip()
-    if not os.path.isabs(rt) or not os.path.exists(rt):
-        pytest.skip("the ASan runtime of g++ is not installed")
-    link = [] if shared else ["-static-libasan", "-static-libubsan"]
-    hip_inc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
-    if not os.path.exists(os.path.join(hip_inc, "hip", "hip_runtime.h")):
-        pytest.skip("HIP headers not found")
-    exe = str(tmp_path / "speckle_check")
-    csrc = os.path.join(ROOT, "forest-slam_amd", "csrc")
-    san = os.path.join(ROOT, "tests", "sanitize")
-    cmd = [gxx, "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", "-g", "-O1", "-D__HIP_PLATFORM_AMD__", "-I", hip_inc,
-           "-I", os.path.join(ROOT, "include"), os.path.join(csrc, "capi.cpp"), os.path.join(csrc, "speckle_api.cpp"),
-           os.path.join(san, "host_stubs.cpp"), os.path.join(san, "speckle_check.cpp"), "-o", exe] + link
-    b = subprocess.run(cmd, capture_output=True, text=True)
-    assert b.returncode == 0, b.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([exe], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
-    assert "0 failed" in r.stdout
+    """fvo_filter_speckles and fvo_speckle_workspace_bytes of csrc/capi.cpp (every error path, the
+    no-launch cases, the workspace arithmetic) as a stand-alone ASan + UBSan program:
+    tests/sanitize/speckle_check.cpp."""
+    run_check("speckle_check", tmp_path)
 
 
 def test_shim_accepts_speckle_arguments_and_refuses_uint8():
