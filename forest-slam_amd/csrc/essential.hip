@@ -890,12 +890,15 @@ __global__ __launch_bounds__(64) void k_em_roots(int maxIters, int it_lo, const 
 // Scoring: every (subset, model) pair of the block's 64 subsets spread evenly over the lanes,
 // the points staged in LDS.
 constexpr int EM_SC_THREADS = 256, EM_SC_PARTS = 4;  // scoring block; lanes per (subset, model) pair
+constexpr int kEmModelSlots = 640;                   // 64 subsets x at most 10 models
 __global__ __launch_bounds__(EM_SC_THREADS) void k_em_hyp(const double* __restrict__ xn, int cap, float thr2,
                                                           int maxIters, int it_lo, const EmState* __restrict__ state,
                                                           const double* __restrict__ models,
                                                           int32_t* __restrict__ good, const int8_t* __restrict__ nmod) {
   extern __shared__ __attribute__((aligned(16))) double sx[];  // [n][4]
-  __shared__ int mlist[640];                                   // (subset << 4 | model) of the block's models
+  // 16-bit entries: with 32-bit ones the static LDS (2560 B + s_total, rounded up to the dynamic
+  // array's alignment) pushed a cap of kEmMaxCap 16 B past the 160 KB a block may hold
+  __shared__ uint16_t mlist[kEmModelSlots];  // (subset << 4 | model) of the block's models
   __shared__ int s_total;
   const int b = blockIdx.y, tid = threadIdx.x;
   const EmState st = state[b];
@@ -914,14 +917,14 @@ __global__ __launch_bounds__(EM_SC_THREADS) void k_em_hyp(const double* __restri
     }
     if (tid == 63) s_total = off;
     off -= count;
-    for (int k = 0; k < count; ++k) mlist[off + k] = (tid << 4) | k;
+    for (int k = 0; k < count; ++k) mlist[off + k] = (uint16_t)((tid << 4) | k);
   }
   __syncthreads();
   // EM_SC_PARTS consecutive lanes per pair, each counting every EM_SC_PARTS-th point (integer
   // counts: the sum is order-free)
   const int total = s_total, part = tid % EM_SC_PARTS;
   for (int m0 = tid / EM_SC_PARTS; m0 < total; m0 += EM_SC_THREADS / EM_SC_PARTS) {  // uniform per pair's lanes
-    const int ml = mlist[m0];
+    const int ml = (int)mlist[m0];
     const int who = ml >> 4, k = ml & 15;
     const int64_t s2 = (int64_t)b * maxIters + it_lo + blockIdx.x * 64 + who;
     const double* mE = models + s2 * 90 + k * 9;
@@ -1118,7 +1121,10 @@ int essential_run(fvo_ctx* ctx, const float* p0, const float* p1, const int32_t*
   const float thr2 = (float)(thr * thr);
   EmState* st = (EmState*)ctx->em_state;
   const size_t shm = (size_t)cap * 4 * sizeof(double);
-  static_assert((size_t)kEmMaxCap * 4 * sizeof(double) + 640 * sizeof(int) == 160 * 1024, "kEmMaxCap: k_em_hyp's LDS");
+  // dynamic points + static model list and count, the latter rounded up to the points' 16 B
+  static_assert((size_t)kEmMaxCap * 4 * sizeof(double) + (kEmModelSlots * sizeof(uint16_t) + sizeof(int) + 15) / 16 * 16 <=
+                    160 * 1024,
+                "kEmMaxCap: k_em_hyp's LDS");
   if (shm > 64 * 1024)
     FVO_HIP(ctx, hipFuncSetAttribute((const void*)k_em_hyp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
   // round 1: the first 128 subsets of every frame (the adaptive bound usually ends below)

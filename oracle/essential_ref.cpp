@@ -380,8 +380,11 @@ static void null3(const double* B, double* v) {
 }
 
 // EMEstimatorCallback::runKernel on 5 normalised correspondences (x1[2i], x1[2i+1]) etc.
-// Writes up to 10 models (9 doubles each, row-major E) and returns their count.
-static int five_point(const double* x1, const double* x2, double* models) {
+// Writes up to 10 models (9 doubles each, row-major E) and returns their count.  degree
+// (optional): the degree solvePoly solved, 10 unless leading coefficients were trimmed; -1 when
+// the elimination failed before the polynomial.
+static int five_point(const double* x1, const double* x2, double* models, int* degree = nullptr) {
+  if (degree) *degree = -1;
   double Q[45];
   for (int i = 0; i < 5; ++i) {
     double a = x1[2 * i], b = x1[2 * i + 1], c = x2[2 * i], d = x2[2 * i + 1];
@@ -409,6 +412,7 @@ static int five_point(const double* x1, const double* x2, double* models) {
   det_poly(b, c);
   Cx roots[10];
   int nr = solve_poly(c, roots);
+  if (degree) *degree = nr;
   int count = 0;
   for (int i = 0; i < nr; ++i) {
     if (std::fabs(roots[i].im) > 1e-10) continue;
@@ -644,9 +648,15 @@ int ref_five_point(const double* x1, const double* x2, double* models) { return 
 // findEssentialMat(p1, p2, focal, pp, RANSAC, prob, threshold, maxIters).
 // Returns 1 (E, mask written), 0 RANSAC found nothing, -1 fewer than 5 points,
 // -2 exactly 5 points with several solutions (E would be 3k x 3; recoverPose raises).
-int ref_find_essential(const float* p1, const float* p2, int n, double focal, double cx, double cy, double prob,
-                       double threshold, int max_iters, double* E, uint8_t* mask, int32_t* n_iters_out,
-                       int32_t* best_good_out) {
+// subset_stats (optional, int32[2]): the number of 5-point subsets whose degree-10 polynomial
+// was trimmed to a lower degree, and the number that yielded no model.
+int ref_find_essential_ex(const float* p1, const float* p2, int n, double focal, double cx, double cy, double prob,
+                          double threshold, int max_iters, double* E, uint8_t* mask, int32_t* n_iters_out,
+                          int32_t* best_good_out, int32_t* subset_stats) {
+  int32_t stats_local[2];
+  int32_t* stats = subset_stats ? subset_stats : stats_local;
+  stats[0] = stats[1] = 0;
+  int degree;
   if (n_iters_out) *n_iters_out = 0;
   if (best_good_out) *best_good_out = 0;
   if (n < 5) return -1;
@@ -657,7 +667,9 @@ int ref_find_essential(const float* p1, const float* p2, int n, double focal, do
   float thr2 = (float)(thr * thr);
   double models[90];
   if (n == 5) {
-    int nm = em::five_point(x1.data(), x2.data(), models);
+    int nm = em::five_point(x1.data(), x2.data(), models, &degree);
+    stats[0] += degree >= 0 && degree < 10;
+    stats[1] += nm <= 0;
     if (nm <= 0) return 0;
     if (nm > 1) return -2;
     std::memcpy(E, models, 9 * sizeof(double));
@@ -683,7 +695,9 @@ int ref_find_essential(const float* p1, const float* p2, int n, double focal, do
       s1[2 * i] = x1[2 * j]; s1[2 * i + 1] = x1[2 * j + 1];
       s2[2 * i] = x2[2 * j]; s2[2 * i + 1] = x2[2 * j + 1];
     }
-    int nm = em::five_point(s1, s2, models);
+    int nm = em::five_point(s1, s2, models, &degree);
+    stats[0] += degree >= 0 && degree < 10;
+    stats[1] += nm <= 0;
     for (int k = 0; k < nm; ++k) {
       int good = em::find_inliers(models + 9 * k, x1.data(), x2.data(), n, thr2, m.data());
       if (good > std::max(maxGood, 4)) {
@@ -699,6 +713,13 @@ int ref_find_essential(const float* p1, const float* p2, int n, double focal, do
   if (maxGood <= 0) return 0;
   std::memcpy(mask, best.data(), n);
   return 1;
+}
+
+int ref_find_essential(const float* p1, const float* p2, int n, double focal, double cx, double cy, double prob,
+                       double threshold, int max_iters, double* E, uint8_t* mask, int32_t* n_iters_out,
+                       int32_t* best_good_out) {
+  return ref_find_essential_ex(p1, p2, n, focal, cx, cy, prob, threshold, max_iters, E, mask, n_iters_out,
+                               best_good_out, nullptr);
 }
 
 // recoverPose(E, p1, p2, focal, pp) with distanceThresh; returns the cheirality count.

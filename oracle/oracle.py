@@ -53,10 +53,13 @@ def lib():
         L.ref_fast_atan2.argtypes = [ctypes.c_float, ctypes.c_float]
         L.ref_bf_match.restype = ctypes.c_int
         L.ref_solve_pnp_ransac.restype = ctypes.c_int
+        L.ref_solve_pnp_ransac_ex.restype = ctypes.c_int
         L.ref_find_essential.restype = ctypes.c_int
         L.ref_find_essential.argtypes = [_f32p, _f32p, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                          ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, _f64p,
                                          _u8p, _i32p, _i32p]
+        L.ref_find_essential_ex.restype = ctypes.c_int
+        L.ref_find_essential_ex.argtypes = L.ref_find_essential.argtypes + [_i32p]
         L.ref_recover_pose.restype = ctypes.c_int
         L.ref_recover_pose.argtypes = [_f64p, _f32p, _f32p, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_double, ctypes.c_double, _f64p, _f64p]
@@ -213,9 +216,15 @@ def disparity_map_np1(disp16: np.ndarray) -> np.ndarray:
     return d
 
 
+PNP_KEPT_RANSAC, PNP_DLT, PNP_PLANAR = 0, 1, 2  # refinement initialisation of solve_pnp_ransac(info=True)
+
+
 def solve_pnp_ransac(P3: np.ndarray, p2: np.ndarray, K: np.ndarray, dist: np.ndarray, reproj: float = 1.0,
-                     confidence: float = 0.99, iters: int = 1000):
-    """Returns (ok, rvec, tvec, inlier_idx, ransac_iters, ransac_inliers)."""
+                     confidence: float = 0.99, iters: int = 1000, info: bool = False):
+    """Returns (ok, rvec, tvec, inlier_idx, ransac_iters, ransac_inliers).  info: also a dict
+    with the refinement that ran: branch (PNP_KEPT_RANSAC: the DLT would throw and the RANSAC
+    model is returned, PNP_DLT, PNP_PLANAR: homography init), lm_iters, rt_identity (the planar
+    branch replaced R_transform by the identity), homography_failed."""
     P3 = np.ascontiguousarray(P3, dtype=np.float64)
     p2 = np.ascontiguousarray(p2, dtype=np.float32)
     K = np.ascontiguousarray(K, dtype=np.float64)
@@ -226,17 +235,22 @@ def solve_pnp_ransac(P3: np.ndarray, p2: np.ndarray, K: np.ndarray, dist: np.nda
     mask = np.zeros(max(n, 1), np.uint8)
     ni = np.zeros(1, np.int32)
     bg = np.zeros(1, np.int32)
-    ok = lib().ref_solve_pnp_ransac(_p(P3, _f64p), _p(p2, _f32p), n, _p(K, _f64p), _p(dist, _f64p), iters,
-                                    ctypes.c_float(reproj), ctypes.c_double(confidence), _p(rv, _f64p),
-                                    _p(tv, _f64p), _p(mask, _u8p), _p(ni, _i32p), _p(bg, _i32p))
-    return bool(ok), rv, tv, np.nonzero(mask[:n])[0].astype(np.int32), int(ni[0]), int(bg[0])
+    ri = np.zeros(4, np.int32)
+    ok = lib().ref_solve_pnp_ransac_ex(_p(P3, _f64p), _p(p2, _f32p), n, _p(K, _f64p), _p(dist, _f64p), iters,
+                                       ctypes.c_float(reproj), ctypes.c_double(confidence), _p(rv, _f64p),
+                                       _p(tv, _f64p), _p(mask, _u8p), _p(ni, _i32p), _p(bg, _i32p), _p(ri, _i32p))
+    res = (bool(ok), rv, tv, np.nonzero(mask[:n])[0].astype(np.int32), int(ni[0]), int(bg[0]))
+    if info:
+        res += (dict(branch=int(ri[0]), lm_iters=int(ri[1]), rt_identity=bool(ri[2]), homography_failed=bool(ri[3])),)
+    return res
 
 
 def find_essential(p1: np.ndarray, p2: np.ndarray, focal: float, pp, prob: float = 0.999, threshold: float = 1.0,
-                   max_iters: int = 1000):
+                   max_iters: int = 1000, stats: bool = False):
     """cv2.findEssentialMat(p1, p2, focal=, pp=, RANSAC, prob, threshold) (mono_slam.py:111).
     Returns (status, E 3x3, inlier mask u8[n], ransac_iters, ransac_inliers); status 1 ok,
-    0 RANSAC failed, -1 fewer than 5 points, -2 five points with several solutions."""
+    0 RANSAC failed, -1 fewer than 5 points, -2 five points with several solutions.  stats: also
+    (subsets whose degree-10 polynomial was trimmed to a lower degree, subsets without a model)."""
     p1 = np.ascontiguousarray(p1, dtype=np.float32).reshape(-1, 2)
     p2 = np.ascontiguousarray(p2, dtype=np.float32).reshape(-1, 2)
     n = len(p1)
@@ -244,9 +258,12 @@ def find_essential(p1: np.ndarray, p2: np.ndarray, focal: float, pp, prob: float
     mask = np.zeros(max(n, 1), np.uint8)
     ni = np.zeros(1, np.int32)
     bg = np.zeros(1, np.int32)
-    st = lib().ref_find_essential(_p(p1, _f32p), _p(p2, _f32p), n, focal, float(pp[0]), float(pp[1]), prob,
-                                  threshold, max_iters, _p(E, _f64p), _p(mask, _u8p), _p(ni, _i32p), _p(bg, _i32p))
-    return int(st), E.reshape(3, 3), mask[:n], int(ni[0]), int(bg[0])
+    ss = np.zeros(2, np.int32)
+    st = lib().ref_find_essential_ex(_p(p1, _f32p), _p(p2, _f32p), n, focal, float(pp[0]), float(pp[1]), prob,
+                                     threshold, max_iters, _p(E, _f64p), _p(mask, _u8p), _p(ni, _i32p), _p(bg, _i32p),
+                                     _p(ss, _i32p))
+    res = (int(st), E.reshape(3, 3), mask[:n], int(ni[0]), int(bg[0]))
+    return res + ((int(ss[0]), int(ss[1])),) if stats else res
 
 
 def recover_pose(E: np.ndarray, p1: np.ndarray, p2: np.ndarray, focal: float, pp, dist: float = 50.0):

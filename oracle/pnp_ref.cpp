@@ -587,8 +587,12 @@ static bool homography_dlt(const double* src, const double* dst, int n, double* 
 }
 
 // cvFindExtrinsicCameraParams2(useExtrinsicGuess=false): init + LM.  Returns false if
-// the DLT would throw (non-planar and < 6 points).
-static bool find_extrinsic(const Cam& K, const double* M, const double* m, int n, double* rvec, double* tvec) {
+// the DLT would throw (non-planar and < 6 points).  info (optional, int32[4]): the initialisation
+// that ran (0 none: the DLT would throw, 1 DLT, 2 planar homography), the LM iteration count,
+// whether the planar branch replaced R_transform by the identity, whether the homography failed.
+static bool find_extrinsic(const Cam& K, const double* M, const double* m, int n, double* rvec, double* tvec,
+                           int32_t* info = nullptr) {
+  if (info) info[0] = info[1] = info[2] = info[3] = 0;
   std::vector<double> mn(2 * n);
   for (int i = 0; i < n; ++i) undistort_point(K, m[2 * i], m[2 * i + 1], &mn[2 * i]);
   double param[6] = {0, 0, 0, 0, 0, 0};
@@ -610,7 +614,11 @@ static bool find_extrinsic(const Cam& K, const double* M, const double* m, int n
     double Rt[9];
     for (int i = 0; i < 3; ++i)
       for (int j = 0; j < 3; ++j) Rt[i * 3 + j] = V3[j * 3 + i];
-    if (Rt[2] * Rt[2] + Rt[5] * Rt[5] < 1e-10) { for (int i = 0; i < 9; ++i) Rt[i] = (i % 4 == 0); }
+    if (info) info[0] = 2;
+    if (Rt[2] * Rt[2] + Rt[5] * Rt[5] < 1e-10) {
+      for (int i = 0; i < 9; ++i) Rt[i] = (i % 4 == 0);
+      if (info) info[2] = 1;
+    }
     if (det3(Rt) < 0) for (int i = 0; i < 9; ++i) Rt[i] = -Rt[i];
     double T[3];
     for (int i = 0; i < 3; ++i) T[i] = -(Rt[i * 3] * Mc[0] + Rt[i * 3 + 1] * Mc[1] + Rt[i * 3 + 2] * Mc[2]);
@@ -641,10 +649,12 @@ static bool find_extrinsic(const Cam& K, const double* M, const double* m, int n
       param[3] = t[0]; param[4] = t[1]; param[5] = t[2];
     } else {
       for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0);
+      if (info) info[3] = 1;
     }
     rodrigues_R2r(R, param);
   } else {
     if (n < 6) return false;
+    if (info) info[0] = 1;
     double LL[144] = {0};
     for (int i = 0; i < n; ++i) {
       double x = -mn[2 * i], y = -mn[2 * i + 1];
@@ -736,6 +746,7 @@ static bool find_extrinsic(const Cam& K, const double* M, const double* m, int n
     prevErrNorm = errNorm;
   }
   for (int i = 0; i < 3; ++i) { rvec[i] = param[i]; tvec[i] = param[3 + i]; }
+  if (info) info[1] = iters;
   return true;
 }
 
@@ -746,9 +757,12 @@ extern "C" {
 // solvePnPRansac(P3 f64[n,3], p2 f32[n,2], K, dist(5), 1.0, 0.99, 1000, ITERATIVE).
 // Returns 1 on success (rvec/tvec/inlier mask written), 0 on failure.
 // n_iters_out: RANSAC iterations actually run (debug), best_good_out: RANSAC inliers.
-int ref_solve_pnp_ransac(const double* P3d, const float* p2, int n, const double* Kmat, const double* dist,
-                         int max_iters, float reproj, double confidence, double* rvec, double* tvec,
-                         uint8_t* inlier_mask, int32_t* n_iters_out, int32_t* best_good_out) {
+// refine_info (optional, int32[4]): find_extrinsic's info (all zero when no refinement ran).
+int ref_solve_pnp_ransac_ex(const double* P3d, const float* p2, int n, const double* Kmat, const double* dist,
+                            int max_iters, float reproj, double confidence, double* rvec, double* tvec,
+                            uint8_t* inlier_mask, int32_t* n_iters_out, int32_t* best_good_out,
+                            int32_t* refine_info) {
+  if (refine_info) refine_info[0] = refine_info[1] = refine_info[2] = refine_info[3] = 0;
   pnp::Cam K{Kmat[0], Kmat[4], Kmat[2], Kmat[5], {dist[0], dist[1], dist[2], dist[3], dist[4]}};
   std::vector<float> P3(3 * n);
   for (int i = 0; i < 3 * n; ++i) P3[i] = (float)P3d[i];
@@ -803,13 +817,20 @@ int ref_solve_pnp_ransac(const double* P3d, const float* p2, int n, const double
     }
   int ni = (int)Mi.size() / 3;
   double rv[3], tv[3];
-  bool ok = pnp::find_extrinsic(K, Mi.data(), mi.data(), ni, rv, tv);
+  bool ok = pnp::find_extrinsic(K, Mi.data(), mi.data(), ni, rv, tv, refine_info);
   if (!ok) {
     for (int i = 0; i < 3; ++i) { rv[i] = bestModel[i]; tv[i] = bestModel[3 + i]; }
   }
   for (int i = 0; i < 3; ++i) { rvec[i] = rv[i]; tvec[i] = tv[i]; }
   std::memcpy(inlier_mask, best.data(), n);
   return 1;
+}
+
+int ref_solve_pnp_ransac(const double* P3d, const float* p2, int n, const double* Kmat, const double* dist,
+                         int max_iters, float reproj, double confidence, double* rvec, double* tvec,
+                         uint8_t* inlier_mask, int32_t* n_iters_out, int32_t* best_good_out) {
+  return ref_solve_pnp_ransac_ex(P3d, p2, n, Kmat, dist, max_iters, reproj, confidence, rvec, tvec, inlier_mask,
+                                 n_iters_out, best_good_out, nullptr);
 }
 
 // Debug: the RANSAC hypotheses of the first `iters` iterations (EPnP model per subset and its
