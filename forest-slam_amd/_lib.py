@@ -83,6 +83,10 @@ SIGNATURES = {
     "fvo_voxel_down_sample": (ctypes.c_int, [_P, _P, _L, ctypes.c_double, _P, _L, _P, _P, _P, _P]),
     "fvo_speckle_workspace_bytes": (ctypes.c_int64, [_I, _I, _I]),
     "fvo_filter_speckles": (ctypes.c_int, [_P, _P, _I, _I, _I, _L, _I, _I, _I, _I, _P, _L, _P]),
+    "fvo_dense_workspace_bytes": (ctypes.c_int64, [_I, _I, _I, _I]),
+    "fvo_dense_map_append": (ctypes.c_int, [_P, _P, _I, _I, _I, _L, _I, _P, ctypes.c_double, _I, _I, ctypes.c_float,
+                                            ctypes.c_float, _P, _P, _P, _L, _P, _P, _P, _P, _L, _P]),
+    "fvo_reproject_to_3d": (ctypes.c_int, [_P, _P, _I, _I, _I, _I, _L, _I, _P, _I, _P, _P, _P]),
     "fvo_motion_blur": (ctypes.c_int, [_P, _P, _I, _L, _I, _I, ctypes.c_double, _P, _P, _I, _P, _P, _L, _I, _P]),
     "fvo_test_retain_best": (ctypes.c_int, [_P, _P, _I, _I, _P, _P, _P]),
     "fvo_debug_buffer": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
@@ -555,6 +559,91 @@ class Context:
                                                int(max_speckle_size), int(max_diff), _ptr(workspace),
                                                workspace.numel(), _stream(self.device)))
         return disp
+
+    @staticmethod
+    def _image_view(t, name):
+        """(3-d view, B, H, W, image stride, row pitch) of a [B,H,W] / [H,W] tensor whose rows are
+        element-contiguous (e.g. a column range of a wider buffer)."""
+        if t.dim() not in (2, 3):
+            raise TypeError(f"{name}: expected [B,H,W] or [H,W]")
+        t3 = t if t.dim() == 3 else t[None]
+        B, H, W = t3.shape
+        if W > 1 and t3.stride(2) != 1:
+            raise ValueError(f"{name}: the last dimension must be contiguous")
+        pitch = t3.stride(1) if H > 1 else W
+        istride = t3.stride(0) if B > 1 else pitch * H
+        return t3, B, H, W, istride, pitch
+
+    def dense_workspace_bytes(self, batch: int, height: int, width: int, step: int = 1) -> int:
+        """fvo_dense_workspace_bytes: scratch bytes of dense_map_append for [batch, height, width]."""
+        wb = int(self.L.fvo_dense_workspace_bytes(int(batch), int(height), int(width), int(step)))
+        if wb < 0:
+            raise ValueError(f"dense_map_append: unsupported size batch={batch} {width}x{height} step={step}")
+        return wb
+
+    def dense_map_append(self, disp, K, baseline, T, map_count, map_xyz64=None, map_xyz32=None, step=1,
+                         min_disp16=1, z_min=0.1, z_max=1000.0, frame_keep=None, n_added=None, workspace=None,
+                         map_cap=None):
+        """Append the disparity maps of a batch to the map as a world-frame point cloud
+        (fvo_dense_map_append): every step-th pixel of every step-th row of int16 [B,H,W] (or
+        [H,W]) device maps, back-projected as backproject() does (float32), kept iff d16 >=
+        min_disp16 and z_min < Z < z_max, transformed by T f64 [B,4,4] (device) as map_transform()
+        does and appended from map_count i32 [1] in frame, then row-major, order.  frame_keep i32
+        [B] (device): 0 = the frame contributes nothing.  disp may be a column range of a wider
+        buffer and is not modified.  workspace: uint8 device tensor of >= dense_workspace_bytes(B,
+        H, W, step) bytes, allocated here (as n_added i32 [B] is) only when none is passed.
+        Returns n_added: the kept samples per frame."""
+        if disp.dtype != torch.int16:
+            raise TypeError("disp must be int16 [B,H,W] or [H,W]")
+        if map_xyz64 is None and map_xyz32 is None:
+            raise ValueError("need map_xyz64 and/or map_xyz32")
+        d3, B, H, W, istride, pitch = self._image_view(disp, "dense_map_append")
+        if n_added is None:
+            n_added = torch.zeros((B,), dtype=torch.int32, device=self.device)
+        elif n_added.dtype != torch.int32 or n_added.numel() < B or not n_added.is_contiguous():
+            raise TypeError("n_added must be a contiguous int32 tensor of >= batch entries")
+        if B == 0 or H == 0 or W == 0:
+            return n_added
+        T = T.to(torch.float64).contiguous()
+        if T.shape != (B, 4, 4):
+            raise ValueError("T must be [B,4,4]")
+        if frame_keep is not None and (frame_keep.dtype != torch.int32 or frame_keep.numel() != B
+                                       or not frame_keep.is_contiguous()):
+            raise TypeError("frame_keep must be a contiguous int32 [B] tensor")
+        wb = self.dense_workspace_bytes(B, H, W, step)
+        if workspace is None:
+            workspace = torch.empty((wb,), dtype=torch.uint8, device=self.device)
+        elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < wb:
+            raise ValueError(f"dense_map_append: workspace must be a contiguous uint8 tensor of >= {wb} bytes")
+        if map_cap is None:
+            map_cap = min(m.shape[0] for m in (map_xyz64, map_xyz32) if m is not None)
+        Kh = (ctypes.c_double * 9)(*[float(v) for v in np.asarray(K, np.float64).reshape(-1)])
+        self._check(self.L.fvo_dense_map_append(self.h, _ptr(d3), B, H, W, istride, pitch, Kh, float(baseline),
+                                                int(step), int(min_disp16), float(z_min), float(z_max),
+                                                _ptr(frame_keep), _ptr(T), _ptr(map_count), int(map_cap),
+                                                _ptr(map_xyz64), _ptr(map_xyz32), _ptr(n_added), _ptr(workspace),
+                                                workspace.numel(), _stream(self.device)))
+        return n_added
+
+    def reproject_to_3d(self, disp, Q, handle_missing=False, out=None):
+        """cv2.reprojectImageTo3D on int16 or float32 [B,H,W] (or [H,W]) device images
+        (fvo_reproject_to_3d) -> f32 [B,H,W,3]; the RAW pixel value is the disparity (int16 maps
+        are not divided by 16, as in cv2).  Q: 4x4."""
+        if disp.dtype not in (torch.int16, torch.float32):
+            raise TypeError("disp must be int16 or float32")
+        d3, B, H, W, istride, pitch = self._image_view(disp, "reproject_to_3d")
+        if out is None:
+            out = torch.empty((B, H, W, 3), dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or out.shape != (B, H, W, 3) or not out.is_contiguous():
+            raise TypeError(f"reproject_to_3d: out must be a contiguous float32 [{B},{H},{W},3] tensor")
+        if B == 0 or H == 0 or W == 0:
+            return out
+        Qh = (ctypes.c_double * 16)(*[float(v) for v in np.asarray(Q, np.float64).reshape(16)])
+        key = torch.empty((B,), dtype=torch.int32, device=self.device) if handle_missing else None
+        self._check(self.L.fvo_reproject_to_3d(self.h, _ptr(d3), int(disp.dtype == torch.float32), B, H, W, istride,
+                                               pitch, Qh, int(bool(handle_missing)), _ptr(key), _ptr(out),
+                                               _stream(self.device)))
+        return out
 
     def gather_matches(self, kp0, kp1, matches, nmatch, out=None):
         """mkpts0/mkpts1 of a BF match list (fvo_gather_matches): (p0 f32[B,cap,2], p1, n i32[B])."""

@@ -1,4 +1,5 @@
-// Every extern "C" entry point of libfvo.so (include/fvo.h) and every refusal that depends only on
+// Every extern "C" entry point of libfvo.so (include/fvo.h; the dense-mapping ones are in
+// capi_dense.cpp, under the same rules) and every refusal that depends only on
 // the arguments, fvo_config and host fields of fvo_ctx: config checks (check_<stage>_config, run by
 // fvo_create before the first allocation), argument checks, context lifetime, dispatch to the
 // per-stage launchers.  Host-only: links against tests/sanitize/host_stubs.cpp for the sanitizer

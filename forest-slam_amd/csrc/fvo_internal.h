@@ -216,6 +216,24 @@ int voxel_run(fvo_ctx* ctx, const double* pts, int64_t n, double voxel, void* ws
 // [batch][H*W] (fvo_speckle_workspace_bytes).
 int speckle_run(fvo_ctx* ctx, int16_t* disp, int batch, int H, int W, int64_t image_stride, int pitch, int new_val,
                 int max_speckle_size, int max_diff, void* ws, hipStream_t s);
+// Dense stereo mapping (dense.hip; arguments validated by capi_dense.cpp).  A frame's samples
+// (every step-th pixel of every step-th row, row-major) are cut into blocks of kDenseBlock; ws:
+// [int64 map base][int64 offset per block][int32 count per block] over batch * blocks
+// (fvo_dense_workspace_bytes).
+constexpr int kDenseBlock = 1024;  // 256 threads x 4 consecutive samples
+inline int64_t dense_frame_samples(int H, int W, int step) {
+  return (int64_t)((H - 1) / step + 1) * ((W - 1) / step + 1);
+}
+inline int64_t dense_frame_blocks(int H, int W, int step) {
+  return (dense_frame_samples(H, W, step) + kDenseBlock - 1) / kDenseBlock;
+}
+int dense_append_run(fvo_ctx* ctx, const int16_t* disp, int batch, int H, int W, int64_t image_stride, int pitch,
+                     const double* K, double baseline, int step, int min_disp16, float z_min, float z_max,
+                     const int32_t* frame_keep, const double* T, int32_t* count, int64_t map_cap, double* out64,
+                     float* out32, int32_t* n_added, void* ws, hipStream_t s);
+// cv2.reprojectImageTo3D (dense.hip).  min_key: [batch] u32, used with handle_missing only.
+int reproject_run(fvo_ctx* ctx, const void* disp, int is_f32, int batch, int H, int W, int64_t image_stride,
+                  int pitch, const double* Q, int handle_missing, uint32_t* min_key, float* out, hipStream_t s);
 int mono_init(fvo_ctx* ctx);
 int gather_run(fvo_ctx* ctx, const float* kp0, const float* kp1, const int32_t* matches, const int32_t* nmatch,
                int batch, int cap, float* p0, float* p1, int32_t* npts, hipStream_t s);

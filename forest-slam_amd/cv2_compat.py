@@ -9,7 +9,8 @@ Face 1 mirrors the OpenCV calls of ros_ws/src/stereo_slam.py:
       (and, beside the reference, DescriptorMatcher_create("BruteForce-Hamming").knnMatch(d0, d1, k)
        for Lowe's ratio test)
     StereoSGBM_create(...).compute(L, R)                        (:108-117)
-      (with OpenCV's speckleWindowSize / speckleRange post-filter, and filterSpeckles itself)
+      (with OpenCV's speckleWindowSize / speckleRange post-filter, filterSpeckles itself, and
+       their usual partner reprojectImageTo3D(disparity, Q))
     ok, rvec, tvec, inliers = solvePnPRansac(P, p, K, dist, ...)  (:294-295)
     R, _ = Rodrigues(rvec)                                      (:298)
 and of ros_ws/src/mono_slam.py:
@@ -378,6 +379,39 @@ def filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf=None):
         if d is not t:
             t.copy_(d)  # (a NumPy array shares t's memory: filtered in place)
     return img, buf
+
+
+CV_32F = 5
+_reproject_cache = _CtxCache()
+
+
+def reprojectImageTo3D(disparity, Q, handleMissingValues=False, ddepth=-1):
+    """cv2.reprojectImageTo3D(disparity, Q[, handleMissingValues[, ddepth]]) -> float32 (H, W, 3)
+    on the GPU (fvo_reproject_to_3d): [X Y Z W]^T = Q [x y d 1]^T in fp64, (X/W, Y/W, Z/W) as
+    float32, OpenCV 4.x's Matx evaluation order.  d is the RAW pixel value: as in cv2, an int16
+    StereoSGBM map (disparity x 16) is NOT divided by 16 -- pass ``disp.astype(np.float32) / 16``
+    for metric depth.  handleMissingValues sets Z = 10000 at the pixels holding the image's
+    minimum.  disparity: int16 or float32 (H, W) NumPy array (-> NumPy array), or a torch tensor
+    [H,W] / [B,H,W] (-> device tensor).  Only ddepth -1 / CV_32F is implemented."""
+    if ddepth not in (-1, CV_32F):
+        raise NotImplementedError("reprojectImageTo3D: only ddepth=-1 / CV_32F is implemented")
+    is_np = not isinstance(disparity, torch.Tensor)
+    t = torch.from_numpy(np.ascontiguousarray(disparity)) if is_np else disparity
+    if t.dtype in (torch.uint8, torch.int32):
+        raise NotImplementedError("reprojectImageTo3D: only CV_16SC1 and CV_32FC1 disparities are implemented")
+    if t.dtype not in (torch.int16, torch.float32) or t.dim() not in (2, 3) or (is_np and t.dim() != 2):
+        raise error(f"reprojectImageTo3D: expected an int16 / float32 single-channel image, got {t.dtype} "
+                    f"{tuple(t.shape)}")
+    Qm = np.asarray(Q, dtype=np.float64)
+    if Qm.shape != (4, 4):
+        raise error("reprojectImageTo3D: Q must be 4x4")
+    dev = _device()
+    ctx = _reproject_cache.get(dev.index, lambda: _lib.Context(64, 64, max_batch=1, stages=_lib.STAGE_BF,
+                                                               kp_capacity=64))
+    out = ctx.reproject_to_3d(t.to(dev), Qm, bool(handleMissingValues))
+    if t.dim() == 2:
+        out = out[0]
+    return out.cpu().numpy() if is_np else out
 
 
 # --------------------------------------------------------------------------- solvePnPRansac

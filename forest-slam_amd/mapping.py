@@ -7,6 +7,8 @@ fvo_voxel_down_sample.
   (PointCloud2, point_step 12).
 * ``PointMap.add_cloud`` — mono_slam.py:144-164 / gt_mapping.py:62-66: one point cloud
   transformed by the pose, ``voxel_down_sample(voxel_size=0.5)``, appended to the map.
+* ``PointMap.add_disparity`` — dense stereo mapping over fvo_dense_map_append (no reference
+  counterpart): whole disparity maps back-projected and appended, optionally voxel-filtered.
 
 The map lives in HBM (fp64 + the float32 record), sized once; the append offset is a device
 counter, so batches append without host synchronisation."""
@@ -28,6 +30,7 @@ class PointMap:
         self.count = torch.zeros((1,), dtype=torch.int32, device=self.dev)
         self._tmp64 = None
         self._ws = None
+        self._dense_ws = None
 
     def __len__(self) -> int:
         n = int(self.count.item())
@@ -76,6 +79,57 @@ class PointMap:
         self.xyz64[base:base + k] = out[:k]
         self.xyz32[base:base + k] = out[:k].to(torch.float32)  # pc2.create_cloud_xyz32
         self.count += k
+
+    def add_disparity(self, disp: torch.Tensor, K, baseline: float, cum, step: int = 1, min_disp16: int = 1,
+                      z_min: float = 0.1, z_max: float = 1000.0, keep: torch.Tensor | None = None,
+                      voxel_size: float | None = None, check: bool = False) -> torch.Tensor:
+        """Dense stereo mapping (fvo_dense_map_append): every step-th pixel of every step-th row
+        of the int16 [B,H,W] device disparity maps (StereoSGBM's x16 values), back-projected with
+        the reference's float32 arithmetic (stereo_slam.py:117-121, :265-289), kept iff d16 >=
+        min_disp16 and z_min < Z < z_max, placed by cum f64 [B,4,4] (each frame's cumulative pose)
+        and appended in frame, then row-major, order.  keep: i32 [B] device tensor, 0 = the frame
+        contributes nothing (frames the reference skips).
+
+        voxel_size=None appends straight into the map, with add_frames' overflow contract
+        (``check=True`` raises right here).  Otherwise the points go into a scratch cloud, through
+        voxel_down_sample(voxel_size), and the result is appended as add_cloud does (host sync).
+        Returns n_added i32 [B] (device): the kept samples of each frame, before any voxel filter."""
+        T = torch.as_tensor(np.asarray(cum, np.float64) if not isinstance(cum, torch.Tensor) else cum,
+                            dtype=torch.float64).to(self.dev).reshape(-1, 4, 4)
+        d3 = disp if disp.dim() == 3 else disp[None]
+        B, H, W = d3.shape
+        wb = self.ctx.dense_workspace_bytes(B, H, W, step)
+        if self._dense_ws is None or self._dense_ws.numel() < wb:
+            self._dense_ws = torch.empty((wb,), dtype=torch.uint8, device=self.dev)
+        kw = dict(step=step, min_disp16=min_disp16, z_min=z_min, z_max=z_max, frame_keep=keep,
+                  workspace=self._dense_ws)
+        if voxel_size is None:
+            n_added = self.ctx.dense_map_append(d3, K, baseline, T, self.count, self.xyz64, self.xyz32, **kw)
+            if check:
+                len(self)
+            return n_added
+        n = B * ((H - 1) // step + 1) * ((W - 1) // step + 1)  # every sample kept
+        if n == 0:
+            return torch.zeros((B,), dtype=torch.int32, device=self.dev)
+        if self._tmp64 is None or self._tmp64.shape[0] < n:
+            self._tmp64 = torch.empty((n, 3), dtype=torch.float64, device=self.dev)
+            self._ws = torch.empty((int(self.ctx.L.fvo_voxel_workspace_bytes(n)),), dtype=torch.uint8,
+                                   device=self.dev)
+        c0 = torch.zeros((1,), dtype=torch.int32, device=self.dev)
+        n_added = self.ctx.dense_map_append(d3, K, baseline, T, c0, self._tmp64[:n], None, **kw)
+        m = int(c0.item())
+        if m == 0:
+            return n_added
+        out, nv, st = self.ctx.voxel_down_sample(self._tmp64[:m], voxel_size, workspace=self._ws)
+        if int(st.item()) != 0:
+            raise RuntimeError("voxel_down_sample: voxel index outside the 21-bit key range")
+        k, base = int(nv.item()), len(self)
+        if base + k > self.capacity:
+            raise RuntimeError(f"PointMap overflow: {base + k} points for capacity {self.capacity}")
+        self.xyz64[base:base + k] = out[:k]
+        self.xyz32[base:base + k] = out[:k].to(torch.float32)
+        self.count += k
+        return n_added
 
     def cloud32(self) -> np.ndarray:
         return self.xyz32[: len(self)].cpu().numpy()

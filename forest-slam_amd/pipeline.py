@@ -71,14 +71,18 @@ def _upload(msgs, dev):
 
 def run_stereo_bag(path: str, batch: int = 32, nfeatures: int = 500, frame_interval: int = 1, ba_window: int = 0,
                    device="cuda:0", K_left=K0, dist_left=DIST_L, K_right=K1, dist_right=DIST_R, baseline=BASELINE,
-                   point_map=None, speckle_window: int = 0, speckle_range: int = 0, match_ratio: float = 0.0):
+                   point_map=None, speckle_window: int = 0, speckle_range: int = 0, match_ratio: float = 0.0,
+                   dense_map=None, dense_step: int = 4, dense_z_max: float = 1000.0):
     """stereo_slam.py's ORB branch over a bag -> (TUM rows f64[n,8], relative T, statuses).
     match_ratio: > 0 keeps only the cross-checked matches that pass Lowe's ratio test at that
     ratio (0 = the reference's matcher).
     speckle_window / speckle_range: StereoSGBM_create's speckleWindowSize / speckleRange (0 = off,
     the reference's get_disparity_map()).
     point_map: a ``mapping.PointMap`` that receives every posed frame's points3D in the map
-    frame (stereo_slam.py:308-318)."""
+    frame (stereo_slam.py:308-318).
+    dense_map: a ``mapping.PointMap`` that receives every posed frame's disparity map as a point
+    cloud (every dense_step-th pixel of every dense_step-th row with a valid disparity and
+    0.1 < Z < dense_z_max), placed by the same poses and frame mask as point_map's sparse points."""
     bag = rosbag.Bag(path)
     pairs = select_stereo_pairs(bag, frame_interval)
     if len(pairs) < 2:
@@ -104,14 +108,17 @@ def run_stereo_bag(path: str, batch: int = 32, nfeatures: int = 500, frame_inter
         T, st = fe.step(L, R)
         Ts.append(T.cpu().numpy())
         sts.append(st.cpu().numpy())
-        if point_map is not None:
+        if point_map is not None or dense_map is not None:
             cums = []
             for i in range(e - s):  # stereo_slam.py:306, frames the reference skips keep cum
                 if sts[-1][i] != -1:
                     cum = np.dot(cum, Ts[-1][i])
                 cums.append(cum.copy())
             keep = torch.from_numpy((sts[-1] != -1).astype(np.int32)).to(dev)
-            point_map.add_frames(fe.P3[:e - s], fe.npts[:e - s] * keep, np.stack(cums))
+            if point_map is not None:
+                point_map.add_frames(fe.P3[:e - s], fe.npts[:e - s] * keep, np.stack(cums))
+            if dense_map is not None:
+                fe.append_dense(dense_map, np.stack(cums), step=dense_step, z_max=dense_z_max, keep=keep)
     T = np.concatenate(Ts)
     st = np.concatenate(sts)
     valid = st != -1

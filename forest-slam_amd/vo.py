@@ -264,6 +264,23 @@ class StereoFrontEnd:
         self.k += 1
         return out, st
 
+    def append_dense(self, point_map, cum, **kw):
+        """Dense stereo mapping of the step just run: ``point_map.add_disparity`` on its disparity
+        maps (``self.disp[:n]``, of the step's previous pairs -- frame i's points3D come from the
+        same map) with cum f64 [n,4,4], on the current stream; kw: add_disparity's (step,
+        min_disp16, z_max, keep, ...).  Returns n_added.
+
+        self.disp is one of two slots; with overlap_sgbm the front stage of step k+2 overwrites it
+        after waiting for main_done[slot], recorded at the end of step() -- before these launches
+        -- so it is recorded again behind them (not under capture, where step() records none)."""
+        n = int(cum.shape[0])
+        if self.k == 0 or n > self.B:
+            raise RuntimeError("append_dense: call it after step(), with that step's n poses")
+        n_added = point_map.add_disparity(self.disp[:n], self.K, self.baseline, cum, **kw)
+        if self.overlap_sgbm and not torch.cuda.is_current_stream_capturing():
+            self.main_done[(self.k - 1) % 2] = torch.cuda.current_stream(self.dev).record_event()
+        return n_added
+
     def _sgbm(self, n):
         """SGBM of the step's previous pairs, then the speckle filter when it is enabled
         (StereoSGBM::compute's order), on the current stream."""

@@ -38,6 +38,10 @@
  *   fvo_voxel_down_sample   <- open3d PointCloud.voxel_down_sample(voxel_size=0.5)
  *                              mono_slam.py:151-155, gt_mapping.py:62-66
  *   fvo_filter_speckles     <- cv2.filterSpeckles / StereoSGBM_create(speckleWindowSize=, speckleRange=)
+ *   fvo_dense_map_append    <- (new) the disparity maps of a batch as one world-frame point cloud: the
+ *                              back-projection of stereo_slam.py:262-289 at every step-th pixel + the
+ *                              map update of :308-318, no reference counterpart
+ *   fvo_reproject_to_3d     <- cv2.reprojectImageTo3D(disparity, Q, handleMissingValues)
  *
  * Conventions
  *  - All array pointers are DEVICE pointers owned by the caller (e.g. torch tensors'
@@ -385,6 +389,51 @@ int64_t fvo_speckle_workspace_bytes(int32_t batch, int32_t height, int32_t width
 int fvo_filter_speckles(fvo_ctx* ctx, int16_t* disparity, int32_t batch, int32_t height, int32_t width,
                         int64_t image_stride, int32_t pitch, int32_t new_val, int32_t max_speckle_size,
                         int32_t max_diff, void* workspace, int64_t workspace_bytes, fvo_stream stream);
+
+/* Dense stereo mapping (any stage; any image size, not tied to the context's): the disparity maps
+ * of `batch` frames appended to the map as one world-frame point cloud, in a deterministic order.
+ * Frame b samples the pixels (y, x) with y = 0, step, 2*step, ... < height and x likewise, in
+ * row-major order; frames in batch order.  A sample's camera-frame point is fvo_backproject's
+ * float32 arithmetic at the integer pixel: d = (float)d16 / 16.f (0 and -1 -> 0.1f),
+ * Z = (float)(K[0]*baseline) / d, X = (((float)x - (float)cx) / (float)fx) * Z, Y likewise.  It is
+ * kept iff d16 >= min_disp16 and z_min < Z < z_max (min_disp16 = -32768, z 0.1 / 1000: the
+ * reference's filter exactly; min_disp16 = 1 drops SGBM's invalid pixels and zero disparities by
+ * value).  The kept point goes through fvo_map_transform's fp64 expression with T[b] and is
+ * appended from *map_count exactly as there: *map_count advances by the total (clamped at
+ * INT32_MAX), points at positions >= map_cap are counted but not written.
+ * disparity:  image b at disparity + b*image_stride, rows `pitch` apart (int16 elements, pitch >=
+ *             width, as fvo_filter_speckles); not modified.  height*width <= INT32_MAX.
+ * K:          host double[9] row-major; baseline in metres (both as fvo_backproject).
+ * frame_keep: device [batch] int32 or NULL; 0 = frame b contributes nothing.
+ * T:          device [batch][16] fp64 row-major.  map_count / map_cap / map_xyz64 / map_xyz32: as
+ *             fvo_map_transform (one of the two arrays may be NULL).
+ * n_added:    device [batch] int32 or NULL: kept samples of each frame.
+ * workspace:  device scratch of fvo_dense_workspace_bytes(batch, height, width, step) bytes
+ *             (caller-owned, 8-byte aligned, needs no clearing); that function returns -1 for sizes
+ *             the call refuses.  With step 1, width % 4 == 0 and 8-byte aligned rows (pointer,
+ *             pitch and image_stride) the disparities are read 8 bytes at a time.
+ * Nothing is allocated; the call is stream-ordered and can be captured into a hipGraph.  Three
+ * launches that are not in the fvo_timing_* table. */
+int64_t fvo_dense_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t step);
+int fvo_dense_map_append(fvo_ctx* ctx, const int16_t* disparity, int32_t batch, int32_t height, int32_t width,
+                         int64_t image_stride, int32_t pitch, const double* K, double baseline, int32_t step,
+                         int32_t min_disp16, float z_min, float z_max, const int32_t* frame_keep, const double* T,
+                         int32_t* map_count, int64_t map_cap, double* map_xyz64, float* map_xyz32, int32_t* n_added,
+                         void* workspace, int64_t workspace_bytes, fvo_stream stream);
+
+/* cv2.reprojectImageTo3D(disparity, Q, handleMissingValues) on `batch` CV_16SC1 (is_float32 0) or
+ * CV_32FC1 (is_float32 1) disparity images (any stage; any image size), OpenCV 4.x's Matx form in
+ * fp64:  h_k = (((0 + Q[k][0] x) + Q[k][1] y) + Q[k][2] d) + Q[k][3],  out_k = (float)(h_k / h_3)
+ * with d the RAW pixel value (cv2 does not divide int16 disparities by 16).  With
+ * handle_missing_values != 0, z = 10000 where |d - min| <= FLT_EPSILON, min the image's minimum
+ * (minMaxIdx), found by a pass of its own.
+ * disparity: image b at disparity + b*image_stride, rows `pitch` apart (in elements).
+ * Q:         host double[16] row-major.
+ * min_key:   device [batch] uint32 scratch, needed (and written) only with handle_missing_values.
+ * out:       [batch][height][width][3] f32. */
+int fvo_reproject_to_3d(fvo_ctx* ctx, const void* disparity, int32_t is_float32, int32_t batch, int32_t height,
+                        int32_t width, int64_t image_stride, int32_t pitch, const double* Q,
+                        int32_t handle_missing_values, uint32_t* min_key, float* out, fvo_stream stream);
 
 /* Test hook: KeyPointsFilter::retainBest on `n` float responses (device memory) with the
  * product's selection kernel.  idx_out [n] receives the surviving original indices in
