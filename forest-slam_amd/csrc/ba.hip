@@ -131,67 +131,10 @@ __device__ __forceinline__ BaWin view(void* base, const BaDims& d, int w) {
 }
 // hdr: [8 + f] per-frame observation list offsets
 
-// exclusive block scan of v (blockDim = kBlock); returns prefix, *total = block sum
-__device__ int block_scan(int v, int* s_tmp, int* total) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) s_tmp[wid] = x;
-  __syncthreads();
-  int pre = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < kBlock / 64; ++k) {
-    if (k < wid) pre += s_tmp[k];
-    tot += s_tmp[k];
-  }
-  __syncthreads();
-  *total = tot;
-  return pre + x - v;
-}
-
-// the same for a block of NT threads
-template <int NT>
-__device__ int block_scan_n(int v, int* s_tmp, int* total) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) s_tmp[wid] = x;
-  __syncthreads();
-  int pre = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < NT / 64; ++k) {
-    if (k < wid) pre += s_tmp[k];
-    tot += s_tmp[k];
-  }
-  __syncthreads();
-  *total = tot;
-  return pre + x - v;
-}
-
-// deterministic block sum of doubles (fixed tree); result valid in every thread
-__device__ double block_sum(double v, double* s_red) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0;
-#pragma unroll
-  for (int k = 0; k < kBlock / 64; ++k) t += s_red[k];
-  __syncthreads();
-  return t;
-}
-
 // ------------------------------------------------------------------ stereo points
 __global__ void k_ba_stereo(const int16_t* __restrict__ disp, const float* __restrict__ kp,
-                            const int32_t* __restrict__ nkp, int W, int H, int cap, double fx, double fy, double cx,
-                            double cy, double fxB, float4* __restrict__ out) {
+                            const int32_t* __restrict__ nkp, int W, int H, int cap, StereoCamF K,
+                            float4* __restrict__ out) {
   const int b = blockIdx.y;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= cap) return;
@@ -201,14 +144,10 @@ __global__ void k_ba_stereo(const int16_t* __restrict__ disp, const float* __res
     const float* a = kp + ((int64_t)b * cap + i) * FVO_KP_STRIDE;
     const float x = a[0], y = a[1];
     int xi = min(max((int)x, 0), W - 1), yi = min(max((int)y, 0), H - 1);
-    const float lo = (float)0.1, hi = 1000.f;
-    float d = (float)disp[((int64_t)b * H + yi) * W + xi] / 16.f;
-    if (d == 0.0f) d = lo;
-    if (d == -1.0f) d = lo;
-    const float Z = (float)fxB / d;
-    const float X = ((x - (float)cx) / (float)fx) * Z;
-    const float Y = ((y - (float)cy) / (float)fy) * Z;
-    if (Z > lo && Z < hi) r = make_float4(X, Y, Z, d);
+    float d, X, Y;
+    const float Z = stereo_depth(disp[((int64_t)b * H + yi) * W + xi], K.fxB, d);
+    stereo_xy(x, y, Z, K, X, Y);
+    if (Z > (float)0.1 && Z < 1000.f) r = make_float4(X, Y, Z, d);
   }
   out[(int64_t)b * cap + i] = r;
 }
@@ -510,17 +449,6 @@ __device__ __forceinline__ bool birth_track(const BaIn& in, const BaDims& dm, co
   return true;
 }
 
-__device__ __forceinline__ int block_isum(int v, int* s_tmp) {  // all threads get the sum
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) s_tmp[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int t = 0;
-#pragma unroll
-  for (int k = 0; k < kBirthBlock / 64; ++k) t += s_tmp[k];
-  __syncthreads();
-  return t;
-}
-
 // (window, birth frame): candidate and observation counts of the frame's rows
 template <bool GMAP>
 __global__ __launch_bounds__(kBirthBlock) void k_ba_births(BaIn in, void* ws, BaDims dm, int first_end,
@@ -544,8 +472,8 @@ __global__ __launch_bounds__(kBirthBlock) void k_ba_births(BaIn in, void* ws, Ba
     float4 sp;
     if (birth_track<GMAP>(in, dm, b, j, r, next, s_tr, len, q, bs, sp)) { ++nl; no += len; }
   }
-  nl = block_isum(nl, s_tmp);
-  no = block_isum(no, s_tmp);
+  nl = block_sum<kBirthBlock>(nl, s_tmp);
+  no = block_sum<kBirthBlock>(no, s_tmp);
   if (threadIdx.x == 0) { v.bld[kBldL + j] = nl; v.bld[kBldO + j] = no; }
 }
 
@@ -584,7 +512,7 @@ __global__ __launch_bounds__(kBirthBlock) void k_ba_emit(BaIn in, void* ws, BaDi
     float4 sp;
     const bool cand = birth_track<GMAP>(in, dm, b, j, r, next, s_tr, len, q, bs, sp);
     int tp;
-    const int packed = block_scan_n<kBirthBlock>((len << 10) | (cand ? 1 : 0), s_tmp, &tp);
+    const int packed = block_scan_excl<kBirthBlock>((len << 10) | (cand ? 1 : 0), s_tmp, tp);
     const int lid = packed & 1023, oof = packed >> 10;
     const bool ok = cand && L0 + lid < dm.Lmax && O0 + oof + len <= dm.Omax;
     if (ok) {
@@ -619,8 +547,8 @@ __global__ __launch_bounds__(kBirthBlock) void k_ba_emit(BaIn in, void* ws, BaDi
     O0 += tp >> 10;
     if (L0 >= dm.Lmax || O0 >= dm.Omax) break;  // uniform: the rest fails
   }
-  okl = block_isum(okl, s_tmp);
-  oko = block_isum(oko, s_tmp);
+  okl = block_sum<kBirthBlock>(okl, s_tmp);
+  oko = block_sum<kBirthBlock>(oko, s_tmp);
   if (tid == 0) {
     atomicAdd(&v.bld[kBldTot], okl);
     atomicAdd(&v.bld[kBldTot + 1], oko);
@@ -676,7 +604,7 @@ __global__ __launch_bounds__(kBirthBlock) void k_ba_lists(BaIn in, void* ws, BaD
     }
     const bool sees = l < L && jl <= k && k < jl + len;
     int tot;
-    const int rank = block_scan_n<kBirthBlock>(sees ? 1 : 0, s_tmp, &tot);
+    const int rank = block_scan_excl<kBirthBlock>(sees ? 1 : 0, s_tmp, tot);
     if (sees) v.flist[pos + rank] = o0 + (k - jl);
     pos += tot;
   }
@@ -709,7 +637,7 @@ __global__ __launch_bounds__(kBlock) void k_ba_cost(BaIn in, void* ws, BaDims dm
       acc += rho;
     }
   }
-  const double t = block_sum(acc, s_red);
+  const double t = block_sum<kBlock>(acc, s_red);
   if (threadIdx.x == 0) v.cp[c] = t;
 }
 
@@ -1448,7 +1376,7 @@ __global__ __launch_bounds__(kBlock) void k_ba_upd(BaIn in, void* ws, BaDims dm,
     }
   }
   for (int m = GLU >> 1; m >= 1; m >>= 1) rho += __shfl_xor(rho, m, 64);
-  const double tot = block_sum(j == 0 ? rho : 0.0, s_red);
+  const double tot = block_sum<kBlock>(j == 0 ? rho : 0.0, s_red);
   if (threadIdx.x == 0) v.cp[c] = tot;
 }
 
@@ -1642,10 +1570,9 @@ int ba_init(fvo_ctx* ctx) {
 int ba_stereo_run(fvo_ctx* ctx, const int16_t* disp, const float* kp, const int32_t* nkp, int batch, int cap,
                   const double* K, double baseline, float* stereo, hipStream_t s) {
   // arguments and config were validated by capi.cpp
-  const double fxB = K[0] * baseline;
   FVO_TIMED(ctx, KN_BA_STEREO, s,
             hipLaunchKernelGGL(k_ba_stereo, dim3((cap + 255) / 256, batch), dim3(256), 0, s, disp, kp, nkp,
-                               ctx->cfg.width, ctx->cfg.height, cap, K[0], K[4], K[2], K[5], fxB,
+                               ctx->cfg.width, ctx->cfg.height, cap, stereo_cam(K, baseline),
                                reinterpret_cast<float4*>(stereo)));
   FVO_LAUNCH_CHECK(ctx);
   return 0;

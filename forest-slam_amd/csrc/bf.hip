@@ -131,9 +131,14 @@ __global__ __launch_bounds__(kRows) void k_bf_pass(const uint8_t* __restrict__ q
     if (s_col[i] != kNoKey) atomicMin(&colkey[(int64_t)b * cap + c0 + i], s_col[i]);
 }
 
-__global__ void k_bf_finish(const int32_t* __restrict__ nq, const int32_t* __restrict__ nt, int cap,
-                            uint32_t* __restrict__ rowkey, uint32_t* __restrict__ colkey,
-                            int32_t* __restrict__ matches, int32_t* __restrict__ nmatch) {
+constexpr int kFinishThreads = 256;  // k_bf_finish, k_bf_ratio
+
+__global__ __launch_bounds__(kFinishThreads) void k_bf_finish(const int32_t* __restrict__ nq,
+                                                              const int32_t* __restrict__ nt, int cap,
+                                                              uint32_t* __restrict__ rowkey,
+                                                              uint32_t* __restrict__ colkey,
+                                                              int32_t* __restrict__ matches,
+                                                              int32_t* __restrict__ nmatch) {
   const int b = blockIdx.x;
   int n0 = nq[b], n1 = nt[b];
   n0 = n0 < 0 ? 0 : (n0 > cap ? cap : n0);
@@ -146,7 +151,7 @@ __global__ void k_bf_finish(const int32_t* __restrict__ nq, const int32_t* __res
   __syncthreads();
   uint32_t* rk = rowkey + (int64_t)b * cap;
   uint32_t* ck = colkey + (int64_t)b * cap;
-  for (int base = 0; base < n0; base += blockDim.x) {
+  for (int base = 0; base < n0; base += kFinishThreads) {
     int q = base + threadIdx.x;
     uint32_t key = kNoKey;
     bool keep = false;
@@ -154,17 +159,10 @@ __global__ void k_bf_finish(const int32_t* __restrict__ nq, const int32_t* __res
       key = rk[q];
       keep = key != kNoKey && (ck[key & 0xFFFFu] & 0xFFFFu) == (uint32_t)q;
     }
-    unsigned long long m = __ballot(keep);
-    int pre = __popcll(m & ((1ull << wave_lane()) - 1ull));
-    if (wave_lane() == 0) s_w[threadIdx.x >> 6] = __popcll(m);
-    __syncthreads();
-    int wpre = 0, tot = 0;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) {
-      if (i < (int)(threadIdx.x >> 6)) wpre += s_w[i];
-      tot += s_w[i];
-    }
+    int tot;
+    const int rank = block_rank<kFinishThreads>(keep, s_w, tot);
     if (keep) {
-      int32_t* o = matches + ((int64_t)b * cap + s_carry + wpre + pre) * 3;
+      int32_t* o = matches + ((int64_t)b * cap + s_carry + rank) * 3;
       o[0] = q;
       o[1] = (int32_t)(key & 0xFFFFu);
       o[2] = (int32_t)(key >> 16);
@@ -175,8 +173,8 @@ __global__ void k_bf_finish(const int32_t* __restrict__ nq, const int32_t* __res
   }
   if (threadIdx.x == 0) nmatch[b] = s_carry;
   // every read of this set's keys is behind the loop's last barrier: reset them for the next call
-  for (int i = threadIdx.x; i < r0; i += blockDim.x) rk[i] = kNoKey;
-  for (int i = threadIdx.x; i < r1; i += blockDim.x) ck[i] = kNoKey;
+  for (int i = threadIdx.x; i < r0; i += kFinishThreads) rk[i] = kNoKey;
+  for (int i = threadIdx.x; i < r1; i += kFinishThreads) ck[i] = kNoKey;
 }
 
 // Keeps the K smallest keys seen, ascending: key falls through the slots, each keeping the smaller.
@@ -260,9 +258,12 @@ __global__ __launch_bounds__(256) void k_bf_knn(const uint8_t* __restrict__ quer
 
 // fwd0 / fwd1: the rows' smallest and second-smallest forward keys; rev (mutual only): the
 // columns' smallest reverse keys (distance << 16 | query index).
-__global__ void k_bf_ratio(const int32_t* __restrict__ nq, int cap, const uint32_t* __restrict__ fwd0,
-                           const uint32_t* __restrict__ fwd1, const uint32_t* __restrict__ rev, double ratio,
-                           int32_t* __restrict__ matches, int32_t* __restrict__ nmatch) {
+__global__ __launch_bounds__(kFinishThreads) void k_bf_ratio(const int32_t* __restrict__ nq, int cap,
+                                                             const uint32_t* __restrict__ fwd0,
+                                                             const uint32_t* __restrict__ fwd1,
+                                                             const uint32_t* __restrict__ rev, double ratio,
+                                                             int32_t* __restrict__ matches,
+                                                             int32_t* __restrict__ nmatch) {
   const int b = blockIdx.x;
   int n0 = nq[b];
   n0 = n0 < 0 ? 0 : (n0 > cap ? cap : n0);
@@ -271,7 +272,7 @@ __global__ void k_bf_ratio(const int32_t* __restrict__ nq, int cap, const uint32
   if (threadIdx.x == 0) s_carry = 0;
   __syncthreads();
   const int64_t off = (int64_t)b * cap;
-  for (int base = 0; base < n0; base += blockDim.x) {
+  for (int base = 0; base < n0; base += kFinishThreads) {
     const int q = base + threadIdx.x;
     uint32_t key = kNoKey;
     bool keep = false;
@@ -282,17 +283,10 @@ __global__ void k_bf_ratio(const int32_t* __restrict__ nq, int cap, const uint32
       keep = k2 != kNoKey && (double)(key >> 16) < ratio * (double)(k2 >> 16);
       if (keep && rev) keep = (rev[off + (key & 0xFFFFu)] & 0xFFFFu) == (uint32_t)q;
     }
-    unsigned long long m = __ballot(keep);
-    int pre = __popcll(m & ((1ull << wave_lane()) - 1ull));
-    if (wave_lane() == 0) s_w[threadIdx.x >> 6] = __popcll(m);
-    __syncthreads();
-    int wpre = 0, tot = 0;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) {
-      if (i < (int)(threadIdx.x >> 6)) wpre += s_w[i];
-      tot += s_w[i];
-    }
+    int tot;
+    const int rank = block_rank<kFinishThreads>(keep, s_w, tot);
     if (keep) {
-      int32_t* o = matches + (off + s_carry + wpre + pre) * 3;
+      int32_t* o = matches + (off + s_carry + rank) * 3;
       o[0] = q;
       o[1] = (int32_t)(key & 0xFFFFu);
       o[2] = (int32_t)(key >> 16);
@@ -332,8 +326,9 @@ int bf_run(fvo_ctx* ctx, const uint8_t* q, const int32_t* nq, const uint8_t* t, 
   const dim3 grid((cap + kRows - 1) / kRows, (cap + kChunk - 1) / kChunk, batch);
   FVO_TIMED(ctx, KN_BF_ARGMIN, s, hipLaunchKernelGGL(k_bf_pass, grid, dim3(kRows), 0, s, q, nq, t, nt, cap,
                                                      ctx->bf_rowkey, ctx->bf_colkey));
-  FVO_TIMED(ctx, KN_BF_FINISH, s, hipLaunchKernelGGL(k_bf_finish, dim3(batch), dim3(256), 0, s, nq, nt, cap,
-                                                     ctx->bf_rowkey, ctx->bf_colkey, matches, nmatch));
+  FVO_TIMED(ctx, KN_BF_FINISH, s,
+            hipLaunchKernelGGL(k_bf_finish, dim3(batch), dim3(kFinishThreads), 0, s, nq, nt, cap, ctx->bf_rowkey,
+                               ctx->bf_colkey, matches, nmatch));
   FVO_LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -361,8 +356,9 @@ int bf_ratio_run(fvo_ctx* ctx, const uint8_t* q, const int32_t* nq, const uint8_
     knn_launch<2, true>(q, nq, t, nt, batch, cap, 2, plane, fwd, s);
     if (mutual) knn_launch<1, true>(t, nt, q, nq, batch, cap, 1, plane, rev, s);
   });
-  FVO_TIMED(ctx, KN_BF_RATIO, s, hipLaunchKernelGGL(k_bf_ratio, dim3(batch), dim3(256), 0, s, nq, cap, fwd, fwd + plane,
-                                                    rev, ratio, matches, nmatch));
+  FVO_TIMED(ctx, KN_BF_RATIO, s,
+            hipLaunchKernelGGL(k_bf_ratio, dim3(batch), dim3(kFinishThreads), 0, s, nq, cap, fwd, fwd + plane, rev,
+                               ratio, matches, nmatch));
   FVO_LAUNCH_CHECK(ctx);
   return 0;
 }

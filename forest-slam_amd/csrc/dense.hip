@@ -2,20 +2,19 @@
 // (fvo_dense_map_append), and cv2.reprojectImageTo3D (fvo_reproject_to_3d).
 //
 // fvo_dense_map_append.  Frame b samples the pixels (y, x), y = 0, step, 2 step, ... < H and x
-// likewise, in row-major order; a sample's camera-frame point is k_backproject's float32
-// arithmetic (pose.hip; stereo_slam.py:117-121, :265-289) at the integer pixel, kept iff
-// d16 >= min_disp16 and z_min < Z < z_max; the kept point goes through fvo_map_transform's fp64
-// expression (map.hip k_map_xform) and is appended at the map's running count, frames in batch
-// order.  The order is deterministic: two passes over the disparities and a scan between them, no
-// block waits for another.
+// likewise, in row-major order; a sample's camera-frame point is the stereo point of fvo_device.h
+// (stereo_slam.py:117-121, :265-289) at the integer pixel, kept iff d16 >= min_disp16 and
+// z_min < Z < z_max; the kept point goes through map_point (fvo_device.h) and is appended at the
+// map's running count, frames in batch order.  The order is deterministic: two passes over the
+// disparities and a scan between them, no block waits for another.
 //   k_dense_count  a frame's flat sample index space in blocks of 256 threads x 4 consecutive
-//                  samples; the block's valid count from wave ballots + an LDS sum.
+//                  samples; the block's valid count (block_rank's total).
 //   k_dense_scan   one block: exclusive offsets over [batch][blocks], the per-frame totals
 //                  (n_added), the map's old count (the base, kept in the workspace) and its
 //                  advanced count (clamped at INT32_MAX).
-//   k_dense_emit   the same predicate again, rank in the block by ballot + popcount + the wave
-//                  prefix, the point, placed at base + offset + rank when below map_cap: the
-//                  block's points meet in LDS in rank order and leave as one contiguous run,
+//   k_dense_emit   the same predicate again, rank in the block (block_rank), the point, placed
+//                  at base + offset + rank when below map_cap: the block's points meet in
+//                  LDS in rank order and leave as one contiguous run,
 //                  lane after lane (stored straight from the sample loop, adjacent lanes were
 //                  ~96 B apart: 0.51 ms per 64 frames at 960x600 against 0.32 staged).
 // At step 1 with width % 4 == 0 and 8-byte aligned rows a thread's four samples are one 8-byte
@@ -42,18 +41,6 @@ struct DenseGrid {
   uint32_t ns;                 // samples per frame
   int64_t stride;
 };
-
-struct DenseCam {
-  float fxB, fx, fy, cx, cy;
-};
-
-// k_backproject's depth: d = d16 / 16, 0 and -1 -> 0.1, Z = fx B / d
-__device__ __forceinline__ float dense_depth(int d16, float fxB) {
-  float d = (float)d16 / 16.f;
-  if (d == 0.0f) d = (float)0.1;
-  if (d == -1.0f) d = (float)0.1;
-  return fxB / d;
-}
 
 // The block's frame and its four samples per thread: disparities, pixel coordinates, the kept
 // flags (both passes evaluate exactly this).  Returns false (uniform) when frame b contributes
@@ -102,7 +89,8 @@ __device__ __forceinline__ void dense_samples(const int16_t* __restrict__ disp, 
   }
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    s.Z[j] = dense_depth(d16[j], fxB);
+    float d;
+    s.Z[j] = stereo_depth(d16[j], fxB, d);
     s.keep[j] = in[j] && d16[j] >= min_disp16 && s.Z[j] > z_min && s.Z[j] < z_max;
   }
 }
@@ -119,13 +107,10 @@ __global__ __launch_bounds__(kDenseThreads) void k_dense_count(const int16_t* __
   }
   DenseSamples s;
   dense_samples<VEC>(disp, g, b, k, fxB, min_disp16, z_min, z_max, s);
-  int wtot = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) wtot += __popcll(__ballot(s.keep[j]));
   __shared__ int s_w[kDenseThreads / 64];
-  if (wave_lane() == 0) s_w[threadIdx.x >> 6] = wtot;
-  __syncthreads();
-  if (threadIdx.x == 0) cnt[blk] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+  int total;
+  block_rank<kDenseThreads>(s.keep, s_w, total);
+  if (threadIdx.x == 0) cnt[blk] = total;
 }
 
 // One block.  Exclusive scan of cnt[n] into off[n] (tiles of 1024 threads x 4 entries, a carry
@@ -137,7 +122,7 @@ __global__ __launch_bounds__(kScanThreads) void k_dense_scan(const int32_t* __re
                                                              int32_t* __restrict__ map_count) {
   __shared__ int64_t s_w[kScanThreads / 64];
   __shared__ int64_t s_carry;
-  const int tid = threadIdx.x, lane = wave_lane(), wave = tid >> 6;
+  const int tid = threadIdx.x, wave = tid >> 6;
   if (tid == 0) s_carry = 0;
   __syncthreads();
   for (int64_t tile = 0; tile < n; tile += 4 * kScanThreads) {
@@ -146,13 +131,8 @@ __global__ __launch_bounds__(kScanThreads) void k_dense_scan(const int32_t* __re
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = i + j < n ? cnt[i + j] : 0;
     const int64_t own = ((int64_t)v[0] + v[1]) + ((int64_t)v[2] + v[3]);
-    int64_t inc = own;  // inclusive scan over the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int64_t up = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += up;
-    }
-    if (lane == 63) s_w[wave] = inc;
+    const int64_t inc = wave_scan_incl(own);
+    if (wave_lane() == 63) s_w[wave] = inc;
     __syncthreads();
     int64_t wpre = 0, tot = 0;
 #pragma unroll
@@ -185,7 +165,7 @@ __global__ __launch_bounds__(kScanThreads) void k_dense_scan(const int32_t* __re
 
 template <bool VEC>
 __global__ __launch_bounds__(kDenseThreads) void k_dense_emit(const int16_t* __restrict__ disp, DenseGrid g,
-                                                              DenseCam cam, int min_disp16, float z_min, float z_max,
+                                                              StereoCamF cam, int min_disp16, float z_min, float z_max,
                                                               const int32_t* __restrict__ frame_keep,
                                                               const double* __restrict__ T,
                                                               const int32_t* __restrict__ cnt,
@@ -200,36 +180,17 @@ __global__ __launch_bounds__(kDenseThreads) void k_dense_emit(const int16_t* __r
   if (o0 >= map_cap) return;
   DenseSamples s;
   dense_samples<VEC>(disp, g, b, k, cam.fxB, min_disp16, z_min, z_max, s);
-  const unsigned long long lt = (1ull << wave_lane()) - 1ull;
-  int pre = 0, wtot = 0;  // kept samples of the lanes before this one, of the wave
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const unsigned long long m = __ballot(s.keep[j]);
-    pre += __popcll(m & lt);
-    wtot += __popcll(m);
-  }
   __shared__ int s_w[kDenseThreads / 64];
   __shared__ double s_pt[3 * kDenseBlock];  // the block's points in rank order (24 KB)
-  if (wave_lane() == 0) s_w[threadIdx.x >> 6] = wtot;
-  __syncthreads();
-  int wpre = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < kDenseThreads / 64; ++w) {
-    if (w < (int)(threadIdx.x >> 6)) wpre += s_w[w];
-    total += s_w[w];
-  }
-  int r = wpre + pre;  // rank in the block
+  int total;
+  int r = block_rank<kDenseThreads>(s.keep, s_w, total);
   const double* M = T + 16 * (int64_t)b;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (!s.keep[j]) continue;
-    const float Zf = s.Z[j];
-    const float Xf = (((float)s.x[j] - cam.cx) / cam.fx) * Zf;
-    const float Yf = (((float)s.y[j] - cam.cy) / cam.fy) * Zf;
-    const double x = Xf, y = Yf, z = Zf;
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-      s_pt[3 * r + q] = ((M[4 * q] * x + M[4 * q + 1] * y) + M[4 * q + 2] * z) + M[4 * q + 3] * 1.0;
+    float X, Y;
+    stereo_xy((float)s.x[j], (float)s.y[j], s.Z[j], cam, X, Y);
+    map_point(M, X, Y, s.Z[j], &s_pt[3 * r]);
     ++r;
   }
   __syncthreads();
@@ -333,7 +294,7 @@ int dense_append_run(fvo_ctx* ctx, const int16_t* disp, int batch, int H, int W,
                      const double* K, double baseline, int step, int min_disp16, float z_min, float z_max,
                      const int32_t* frame_keep, const double* T, int32_t* count, int64_t map_cap, double* out64,
                      float* out32, int32_t* n_added, void* ws, hipStream_t s) {
-  // arguments were validated by capi_dense.cpp (batch * blocks fits an int32, the workspace holds it)
+  // arguments were validated by capi.cpp (batch * blocks fits an int32, the workspace holds it)
   DenseGrid g;
   g.W = W;
   g.nx = (W - 1) / step + 1;
@@ -343,7 +304,7 @@ int dense_append_run(fvo_ctx* ctx, const int16_t* disp, int batch, int H, int W,
   g.ns = (uint32_t)dense_frame_samples(H, W, step);
   g.stride = image_stride;
   const int n = g.nb * batch;
-  const DenseCam cam{(float)(K[0] * baseline), (float)K[0], (float)K[4], (float)K[2], (float)K[5]};
+  const StereoCamF cam = stereo_cam(K, baseline);
   int64_t* base = (int64_t*)ws;
   int64_t* off = base + 1;
   int32_t* cnt = (int32_t*)(off + n);
@@ -372,7 +333,7 @@ int dense_append_run(fvo_ctx* ctx, const int16_t* disp, int batch, int H, int W,
 
 int reproject_run(fvo_ctx* ctx, const void* disp, int is_f32, int batch, int H, int W, int64_t image_stride,
                   int pitch, const double* Q, int handle_missing, uint32_t* min_key, float* out, hipStream_t s) {
-  // arguments were validated by capi_dense.cpp
+  // arguments were validated by capi.cpp
   RpGeom g;
   g.W = W;
   g.pitch = pitch;

@@ -216,7 +216,7 @@ int voxel_run(fvo_ctx* ctx, const double* pts, int64_t n, double voxel, void* ws
 // [batch][H*W] (fvo_speckle_workspace_bytes).
 int speckle_run(fvo_ctx* ctx, int16_t* disp, int batch, int H, int W, int64_t image_stride, int pitch, int new_val,
                 int max_speckle_size, int max_diff, void* ws, hipStream_t s);
-// Dense stereo mapping (dense.hip; arguments validated by capi_dense.cpp).  A frame's samples
+// Dense stereo mapping (dense.hip).  A frame's samples
 // (every step-th pixel of every step-th row, row-major) are cut into blocks of kDenseBlock; ws:
 // [int64 map base][int64 offset per block][int32 count per block] over batch * blocks
 // (fvo_dense_workspace_bytes).

@@ -7,9 +7,9 @@
 //                            pc2.create_cloud_xyz32
 //   gt_mapping.py:62-66      the same with the ground-truth pose
 // Kernels:
-//   k_map_xform   thread per point: x' = ((T00 x + T01 y) + T02 z) + T03 in fp64 (no contraction;
-//                 numpy's dgemm order is unpinned), appended at the map's running count as
-//                 f64 xyz and/or the PointCloud2 float32 xyz record; HBM-bound (12 B in, 24+12 out).
+//   k_map_xform   thread per point: map_point (fvo_device.h) in fp64, appended at the map's running
+//                 count as f64 xyz and/or the PointCloud2 float32 xyz record; HBM-bound (12 B in,
+//                 24+12 out).
 //   k_chain       the pose chain stereo_slam.py:306 on the device (fvo_chain_poses): the map's
 //                 placing poses without a host round trip.
 //   voxel_down_sample (Open3D PointCloud::VoxelDownSample): min bound by block partials, voxel
@@ -47,11 +47,8 @@ __global__ __launch_bounds__(256) void k_map_xform(const float* __restrict__ pts
   const int64_t o = s_base + i;
   if (o >= map_cap) return;
   const float* p = pts + ((int64_t)b * cap + i) * stride;
-  const double x = p[0], y = p[1], z = p[2];
-  const double* M = T + 16 * b;
   double r[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) r[k] = ((M[4 * k] * x + M[4 * k + 1] * y) + M[4 * k + 2] * z) + M[4 * k + 3] * 1.0;
+  map_point(T + 16 * b, p[0], p[1], p[2], r);
   if (out64) {
     out64[3 * o] = r[0];
     out64[3 * o + 1] = r[1];

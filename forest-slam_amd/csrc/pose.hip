@@ -3,9 +3,9 @@
 //   cv2.solvePnPRansac(points3D, mkpts1_l, K0, dist_l, 1.0, 0.99, 1000, ITERATIVE) and
 //   cv2.Rodrigues -> T (:294-303).
 //
-// k_backproject  one thread per match, float32 arithmetic in NumPy 1.x order
-//                (the reference environment's value-based casting),
-//                ordered compaction of 0.1 < Z < 1000 (block scan), one block per frame.
+// k_backproject  one thread per match, the stereo point of fvo_device.h (float32 arithmetic in
+//                NumPy 1.x order: the reference environment's value-based casting, DESIGN.md
+//                §Parity), ordered compaction of 0.1 < Z < 1000 (block_rank), one block per frame.
 // k_pnp          one wavefront per frame.  RANSAC iterations are evaluated 64 at a time:
 //                lane 0 draws the subsets with OpenCV's RNG(-1) (the draws depend only on
 //                the point count), every lane solves EPnP for its subset and scores it over
@@ -28,14 +28,12 @@ namespace {
 constexpr int kChunk = 64;
 
 // ------------------------------------------------------------------ back-projection
-struct CamF {
-  double fx, fy, cx, cy, fxB;
-};
+constexpr int kBackprojectThreads = 256;
 
-__global__ void k_backproject(const int16_t* __restrict__ disp, const float* __restrict__ kp0,
-                              const float* __restrict__ kp1, const int32_t* __restrict__ matches,
-                              const int32_t* __restrict__ nmatch, int W, int H, int cap, CamF K,
-                              float* __restrict__ P3, float* __restrict__ p2, int32_t* __restrict__ npts) {
+__global__ __launch_bounds__(kBackprojectThreads) void k_backproject(
+    const int16_t* __restrict__ disp, const float* __restrict__ kp0, const float* __restrict__ kp1,
+    const int32_t* __restrict__ matches, const int32_t* __restrict__ nmatch, int W, int H, int cap, StereoCamF K,
+    float* __restrict__ P3, float* __restrict__ p2, int32_t* __restrict__ npts) {
   const int b = blockIdx.x;
   int n = nmatch[b];
   n = n < 0 ? 0 : (n > cap ? cap : n);
@@ -43,9 +41,7 @@ __global__ void k_backproject(const int16_t* __restrict__ disp, const float* __r
   __shared__ int s_carry;
   if (threadIdx.x == 0) s_carry = 0;
   __syncthreads();
-  const float fxB = (float)K.fxB, fcx = (float)K.cx, fcy = (float)K.cy, ffx = (float)K.fx, ffy = (float)K.fy;
-  const float lo = (float)0.1, hi = 1000.f;
-  for (int base = 0; base < n; base += blockDim.x) {
+  for (int base = 0; base < n; base += kBackprojectThreads) {
     int i = base + threadIdx.x;
     bool keep = false;
     float X = 0, Y = 0, Z = 0, u = 0, v = 0;
@@ -53,31 +49,20 @@ __global__ void k_backproject(const int16_t* __restrict__ disp, const float* __r
       const int32_t* m = matches + ((int64_t)b * cap + i) * 3;
       const float* a = kp0 + ((int64_t)b * cap + m[0]) * FVO_KP_STRIDE;
       const float* c = kp1 + ((int64_t)b * cap + m[1]) * FVO_KP_STRIDE;
-      float x = a[0], y = a[1];
+      float x = a[0], y = a[1], d;
       int xi = (int)x, yi = (int)y;
       xi = min(max(xi, 0), W - 1);
       yi = min(max(yi, 0), H - 1);
-      float d = (float)disp[((int64_t)b * H + yi) * W + xi] / 16.f;
-      if (d == 0.0f) d = lo;
-      if (d == -1.0f) d = lo;
-      Z = fxB / d;
-      X = ((x - fcx) / ffx) * Z;
-      Y = ((y - fcy) / ffy) * Z;
-      keep = (Z > lo) && (Z < hi);
+      Z = stereo_depth(disp[((int64_t)b * H + yi) * W + xi], K.fxB, d);
+      stereo_xy(x, y, Z, K, X, Y);
+      keep = (Z > (float)0.1) && (Z < 1000.f);
       u = c[0];
       v = c[1];
     }
-    unsigned long long mk = __ballot(keep);
-    int pre = __popcll(mk & ((1ull << wave_lane()) - 1ull));
-    if (wave_lane() == 0) s_w[threadIdx.x >> 6] = __popcll(mk);
-    __syncthreads();
-    int wpre = 0, tot = 0;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) {
-      if (k < (int)(threadIdx.x >> 6)) wpre += s_w[k];
-      tot += s_w[k];
-    }
+    int tot;
+    const int rank = block_rank<kBackprojectThreads>(keep, s_w, tot);
     if (keep) {
-      int o = s_carry + wpre + pre;
+      int o = s_carry + rank;
       float* P = P3 + ((int64_t)b * cap + o) * 3;
       P[0] = X;
       P[1] = Y;
@@ -995,12 +980,6 @@ struct EPnPd {
 using fvo_rs::RNG;
 using fvo_rs::update_num_iters;
 
-__device__ __forceinline__ double wsum_d(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // ------------------------------------------------------------------ RANSAC + refine
 constexpr int kRefineLds = 1024;  // inliers staged in k_pnp_refine's LDS (20 KB)
 
@@ -1134,14 +1113,14 @@ __device__ __attribute__((noinline)) double lm_eval(PnpShared& sh, const Cam K, 
   if (withJ) {
 #pragma unroll
     for (int k = 0; k < 27; ++k) {
-      const double t = wsum_d(a[k]);
+      const double t = wave_sum(a[k]);
       if (lane == 0) {
         if (k < 21) sh.jtj[k] = t;
         else sh.jte[k - 21] = t;
       }
     }
   }
-  return sqrt(wsum_d(a[27]));
+  return sqrt(wave_sum(a[27]));
 }
 
 // The LM step (lane 0): (J^T J with the (1 + lambda) diagonal) x = J^T e from the packed
@@ -1179,7 +1158,7 @@ __device__ void lm_refine(PnpShared& sh, const Cam& K, const float* P3, const fl
     acc[2] += (double)P3[3 * j + 2];
   }
 #pragma unroll
-  for (int k = 0; k < 3; ++k) acc[k] = wsum_d(acc[k]);
+  for (int k = 0; k < 3; ++k) acc[k] = wave_sum(acc[k]);
   double Mc[3] = {acc[0] / n, acc[1] / n, acc[2] / n};
   double MM[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int i = lane; i < n; i += 64) {
@@ -1191,7 +1170,7 @@ __device__ void lm_refine(PnpShared& sh, const Cam& K, const float* P3, const fl
       for (int b = 0; b < 3; ++b) MM[a * 3 + b] += d[a] * d[b];
   }
 #pragma unroll
-  for (int k = 0; k < 9; ++k) MM[k] = wsum_d(MM[k]);
+  for (int k = 0; k < 9; ++k) MM[k] = wave_sum(MM[k]);
   double W3[3], U3[9], V3[9];
   dsvd<3, 3>(MM, W3, U3, V3);
   const bool planar = W3[2] / W3[1] < 1e-3;
@@ -1254,7 +1233,7 @@ __device__ void lm_refine(PnpShared& sh, const Cam& K, const float* P3, const fl
   }
 #pragma unroll
   for (int k = 0; k < 78; ++k) {
-    const double t = wsum_d(LLp[k]);
+    const double t = wave_sum(LLp[k]);
     if (lane == 0) sh.llp[k] = t;  // in LDS: the SVD below runs beside no register copy of it
   }
   __syncthreads();
@@ -1710,10 +1689,9 @@ int backproject_run(fvo_ctx* ctx, const int16_t* disp, const float* kp0, const f
                     const int32_t* nmatch, int batch, int cap, const double* K, double baseline, float* P3, float* p2,
                     int32_t* npts, hipStream_t s) {
   // arguments and config were validated by capi.cpp
-  CamF c{K[0], K[4], K[2], K[5], K[0] * baseline};
-  FVO_TIMED(ctx, KN_BACKPROJECT, s, hipLaunchKernelGGL(k_backproject, dim3(batch), dim3(256), 0, s, disp, kp0, kp1,
-                                                       matches, nmatch, ctx->cfg.width, ctx->cfg.height, cap, c, P3,
-                                                       p2, npts));
+  FVO_TIMED(ctx, KN_BACKPROJECT, s,
+            hipLaunchKernelGGL(k_backproject, dim3(batch), dim3(kBackprojectThreads), 0, s, disp, kp0, kp1, matches,
+                               nmatch, ctx->cfg.width, ctx->cfg.height, cap, stereo_cam(K, baseline), P3, p2, npts));
   FVO_LAUNCH_CHECK(ctx);
   return 0;
 }

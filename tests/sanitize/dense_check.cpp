@@ -1,16 +1,15 @@
-// Argument validation and workspace arithmetic of the dense-mapping C ABI (csrc/capi_dense.cpp:
+// Argument validation and workspace arithmetic of the dense-mapping C ABI (csrc/capi.cpp:
 // fvo_dense_workspace_bytes, fvo_dense_map_append, fvo_reproject_to_3d) exercised on the host
-// under AddressSanitizer + UndefinedBehaviorSanitizer.  Linked with csrc/capi.cpp,
-// csrc/capi_dense.cpp, host_stubs.cpp and dense_stubs.cpp, whose stubs of the launchers record
-// what the entry points passed on (g_dense, g_rp).  Built and run by tests/test_dense_cpu.py.
-// Exit status 0 = all checks passed.
+// under AddressSanitizer + UndefinedBehaviorSanitizer.  Linked with csrc/capi.cpp and
+// host_stubs.cpp, whose stubs of the launchers record what the entry points passed on (g_dense,
+// g_rp).  Built and run by tests/test_dense_cpu.py.  Exit status 0 = all checks passed.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <limits>
 
-#include "dense_stubs.h"
+#include "host_stubs.h"
 
 static int g_fail = 0, g_checks = 0;
 

@@ -82,8 +82,10 @@ def _append(ctx, view, T, count0=0, map_cap=None, step=1, min_disp16=1, z_min=0.
 def test_hand_built_image(ctx, min_disp16):
     """40x24 (one 8-byte group per thread), step 1, T = I: the invalid / zero disparities and
     their neighbours, 2 | 3 and 26100 | 26101 on either side of the depth bounds, the int16
-    extremes, a ramp.  With the reference's filter the float32 cloud is also what the kernel
-    pinned by the oracle, k_backproject, gives for a keypoint at every pixel."""
+    extremes, a ramp.  With the reference's filter the three entry points that compute the stereo
+    point agree with each other, not only each with its oracle: for a keypoint at every pixel,
+    fvo_backproject's points3d, fvo_keypoint_stereo's non-zero rows and the float32 map appended
+    here are the same float32 triples in the same order."""
     from forest_slam_amd import _lib
     img = dr.hand_image()
     H, W = img.shape
@@ -92,18 +94,26 @@ def test_hand_built_image(ctx, min_disp16):
     assert 0 < len(cloud) < H * W
     if min_disp16 != -32768:
         return
-    pctx = _lib.Context(W, H, max_batch=1, stages=_lib.STAGE_POSE, kp_capacity=H * W)
+    pctx = _lib.Context(W, H, max_batch=1, stages=_lib.STAGE_POSE | _lib.STAGE_BA, kp_capacity=H * W, ba_window=3)
     ys, xs = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
     kp = np.zeros((1, H * W, _lib.KP_STRIDE), np.float32)
     kp[0, :, 0], kp[0, :, 1] = xs.ravel(), ys.ravel()
     m = np.zeros((1, H * W, 3), np.int32)
     m[0, :, 0] = m[0, :, 1] = np.arange(H * W)
     kpt = torch.from_numpy(kp).cuda()
-    P3, _, npts = pctx.backproject(dev, kpt, kpt, torch.from_numpy(m).cuda(),
-                                   torch.tensor([H * W], dtype=torch.int32, device="cuda"), dr.HAND_K,
-                                   dr.HAND_BASELINE)
+    nkp = torch.tensor([H * W], dtype=torch.int32, device="cuda")
+    P3, _, npts = pctx.backproject(dev, kpt, kpt, torch.from_numpy(m).cuda(), nkp, dr.HAND_K, dr.HAND_BASELINE)
     assert int(npts.item()) == len(cloud)
     assert np.array_equal(P3[0, :len(cloud)].cpu().numpy(), cloud.astype(np.float32))
+    stereo = pctx.keypoint_stereo(dev, kpt, nkp, dr.HAND_K, dr.HAND_BASELINE)[0].cpu().numpy()
+    m32 = torch.full((len(cloud) + GUARD, 3), SENTINEL, dtype=torch.float32, device="cuda")
+    cnt = torch.zeros(1, dtype=torch.int32, device="cuda")
+    ctx.dense_map_append(dev, dr.HAND_K, dr.HAND_BASELINE, torch.eye(4, dtype=torch.float64, device="cuda")[None],
+                         cnt, None, m32, step=1, min_disp16=-32768, map_cap=len(cloud))
+    assert int(cnt.item()) == len(cloud)
+    a = P3[0, :len(cloud)].cpu().numpy().view(np.uint32)
+    assert np.array_equal(stereo[stereo[:, 2] != 0][:, :3].view(np.uint32), a)
+    assert np.array_equal(m32[:len(cloud)].cpu().numpy().view(np.uint32), a)
 
 
 @pytest.mark.parametrize("step", [1, 2, 3, 5])
