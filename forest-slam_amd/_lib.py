@@ -41,6 +41,7 @@ ABI_VERSION = 7  # FVO_ABI_VERSION of include/fvo.h
 STAGE_ORB, STAGE_BF, STAGE_SGBM, STAGE_POSE, STAGE_BA, STAGE_MONO = 1, 2, 4, 8, 16, 32
 SGBM_CLASSIC, SGBM_LPATH = 0, 1  # fvo_config.sgbm_mode
 SGBM_OK, SGBM_HANDOFF_TIMEOUT = 0, -1  # fvo_sgbm status values
+RECTIFY_TILE_W, RECTIFY_TILE_H, RECTIFY_LDS_BYTES = 64, 16, 8192  # FVO_RECTIFY_* of include/fvo.h
 
 # name -> (restype, argtypes); mirrors include/fvo.h
 _P = ctypes.c_void_p
@@ -75,6 +76,10 @@ SIGNATURES = {
     "fvo_recover_pose": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_double, ctypes.c_double,
                                         ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P]),
     "fvo_undistort_gray": (ctypes.c_int, [_P, _P, _I, _L, _I, _P, _P, _P, _L, _I, _P]),
+    "fvo_rectify_map": (ctypes.c_int, [_P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "fvo_remap_u8": (ctypes.c_int, [_P, _P, _I, _L, _I, _I, _P, _P, _P, _L, _I, _P]),
+    "fvo_rectify_gray": (ctypes.c_int, [_P, _P, _I, _L, _I, _I, _P, _P, _I, _P, _P, _P, _L, _I, _P]),
+    "fvo_rectify_lds_budget": (ctypes.c_int, [_P, _I]),
     "fvo_map_transform": (ctypes.c_int, [_P, _P, _I, _P, _I, _L, _P, _P, _L, _P, _P, _P]),
     "fvo_chain_poses": (ctypes.c_int, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "fvo_copy_regions": (ctypes.c_int, [_P, _I, _P, _P]),
@@ -396,6 +401,101 @@ class Context:
         self._check(self.L.fvo_undistort_gray(self.h, _ptr(bgr), B, H * W * 3, W * 3, Kh, dh, _ptr(out), H * W, W,
                                               _stream(self.device)))
         return out
+
+    def _u8_images(self, t, name, channels=None):
+        """(tensor, B, channels, image stride, row pitch) of u8 images of the context's size:
+        [B,H,W,C], [H,W,C], [B,H,W] or [H,W] (C = 1 or 3), pixels contiguous within a row; rows and
+        images may be spaced (a view of a wider buffer).  A 3-d tensor is [B,H,W] when channels
+        is 1 and [H,W,C] when it is 3; with channels None it is told by its shape ([B,H,W] unless
+        only [H,W,C] fits)."""
+        H, W = self.height, self.width
+        if t.dtype != torch.uint8:
+            raise TypeError(f"{name}: expected a uint8 tensor")
+        if channels not in (None, 1, 3):
+            raise ValueError(f"{name}: channels must be 1 or 3")
+        if t.dim() == 3 and channels is not None:
+            mono = channels == 1 and t.shape[2] != 1
+        else:
+            mono = t.dim() == 3 and tuple(t.shape[1:]) == (H, W) and not (tuple(t.shape[:2]) == (H, W) and
+                                                                          t.shape[2] in (1, 3))
+        if t.dim() == 2 or mono:
+            t = t[..., None]
+        if t.dim() == 3:
+            t = t[None]
+        if t.dim() != 4 or tuple(t.shape[1:3]) != (H, W) or t.shape[3] not in (1, 3):
+            raise ValueError(f"{name}: context is {W}x{H}, expected [B,{H},{W},1|3], got {tuple(t.shape)}")
+        B, C = t.shape[0], t.shape[3]
+        if channels is not None and C != channels:
+            raise ValueError(f"{name}: expected {channels} channel(s), got {C}")
+        if (C > 1 and t.stride(3) != 1) or (W > 1 and t.stride(2) != C):
+            raise ValueError(f"{name}: the pixels of a row must be contiguous")
+        pitch = t.stride(1) if H > 1 else W * C
+        return t, B, C, (t.stride(0) if B > 1 else pitch * H), pitch
+
+    @staticmethod
+    def _lens_args(K, dist, R, newK):
+        d = [float(v) for v in np.asarray(dist, np.float64).reshape(-1)]
+        if len(d) not in (4, 5, 8):
+            raise ValueError("dist must have 4, 5 or 8 coefficients (k1 k2 p1 p2 [k3 [k4 k5 k6]])")
+        m9 = lambda M: None if M is None else (ctypes.c_double * 9)(*[float(v) for v in
+                                                                      np.asarray(M, np.float64).reshape(9)])
+        return m9(K), (ctypes.c_double * len(d))(*d), len(d), m9(R), m9(newK)
+
+    def rectify_map(self, K, dist, R=None, newK=None, out=None):
+        """cv2.initUndistortRectifyMap(K, dist, R, newK, (W, H), CV_16SC2) for the context's image
+        size (fvo_rectify_map) -> (map1 i16 [H,W,2], map2 u16 [H,W]) on the device.  R None = I,
+        newK None = K; dist has 4, 5 or 8 coefficients."""
+        H, W = self.height, self.width
+        if out is None:
+            out = (torch.empty((H, W, 2), dtype=torch.int16, device=self.device),
+                   torch.empty((H, W), dtype=torch.uint16, device=self.device))
+        m1, m2 = out
+        if m1.dtype != torch.int16 or tuple(m1.shape) != (H, W, 2) or not m1.is_contiguous() or \
+                m2.dtype != torch.uint16 or tuple(m2.shape) != (H, W) or not m2.is_contiguous():
+            raise TypeError(f"rectify_map: out must be contiguous (int16 [{H},{W},2], uint16 [{H},{W}])")
+        Kh, dh, nd, Rh, Nh = self._lens_args(K, dist, R, newK)
+        self._check(self.L.fvo_rectify_map(self.h, Kh, dh, nd, Rh, Nh, _ptr(m1), _ptr(m2), _stream(self.device)))
+        return m1, m2
+
+    def remap(self, src, map1, map2, out=None, channels=None):
+        """cv2.remap(src, map1, map2, INTER_LINEAR) with BORDER_CONSTANT 0 (fvo_remap_u8) on u8
+        images [B,H,W,C] / [H,W,C] / [B,H,W] / [H,W], C = 1 or 3 -> u8 [B,H,W,C].  channels (1 or 3)
+        says which layout a 3-d src has where its shape alone cannot (B == H == W)."""
+        H, W = self.height, self.width
+        s, B, C, sstride, spitch = self._u8_images(src, "remap", channels)
+        if map1.dtype != torch.int16 or tuple(map1.shape) != (H, W, 2) or not map1.is_contiguous() or \
+                map2.dtype != torch.uint16 or tuple(map2.shape) != (H, W) or not map2.is_contiguous():
+            raise TypeError(f"remap: the map must be contiguous (int16 [{H},{W},2], uint16 [{H},{W}])")
+        if out is None:
+            out = torch.empty((B, H, W, C), dtype=torch.uint8, device=self.device)
+        o, Bo, Co, dstride, dpitch = self._u8_images(out, "remap out", C if out.dim() == 3 else None)
+        if (Bo, Co) != (B, C):
+            raise ValueError("remap: out must have the batch and channels of src")
+        self._check(self.L.fvo_remap_u8(self.h, _ptr(s), B, sstride, spitch, C, _ptr(map1), _ptr(map2), _ptr(o),
+                                        dstride, dpitch, _stream(self.device)))
+        return out
+
+    def rectify_gray(self, src, K, dist, R=None, newK=None, out=None, channels=None):
+        """The rectifying ingest (fvo_rectify_gray): initUndistortRectifyMap + remap + BGR2GRAY in
+        one kernel, no map stored.  src u8 bgr8 [B,H,W,3] / [H,W,3] or mono8 [B,H,W] / [H,W]
+        -> gray u8 [B,H,W].  channels (1 or 3) says which layout a 3-d src has where its shape
+        alone cannot (B == H == W)."""
+        H, W = self.height, self.width
+        s, B, C, sstride, spitch = self._u8_images(src, "rectify_gray", channels)
+        if out is None:
+            out = torch.empty((B, H, W), dtype=torch.uint8, device=self.device)
+        o, Bo, Co, dstride, dpitch = self._u8_images(out, "rectify_gray out", 1 if out.dim() == 3 else None)
+        if (Bo, Co) != (B, 1):
+            raise ValueError("rectify_gray: out must be [B,H,W] with the batch of src")
+        Kh, dh, nd, Rh, Nh = self._lens_args(K, dist, R, newK)
+        self._check(self.L.fvo_rectify_gray(self.h, _ptr(s), B, sstride, spitch, C, Kh, dh, nd, Rh, Nh, _ptr(o),
+                                            dstride, dpitch, _stream(self.device)))
+        return out
+
+    def rectify_lds_budget(self, nbytes: int):
+        """Measurement / test hook (fvo_rectify_lds_budget): LDS bytes a block of remap /
+        rectify_gray may stage; 0 = every block gathers directly.  The output does not depend on it."""
+        self._check(self.L.fvo_rectify_lds_budget(self.h, int(nbytes)))
 
     def motion_blur(self, img, ksize, centers=None, n_centers=None, angle=0.0, out=None, mask=None):
         """apply_random_motion_blur (stereo_slam.py:142-178) on gray u8 [B,H,W] images.

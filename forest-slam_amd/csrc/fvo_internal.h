@@ -136,6 +136,8 @@ struct fvo_ctx {
   double* em_ws = nullptr;        // [B][max_iters][EM_WS] per-subset solver stages (basis, 10x20, B(z), det)
   void* em_state = nullptr;       // [B] EmState
   int32_t em_max_iters = 0;
+  // rectification (rectify.hip): LDS bytes a block may stage (fvo_rectify_lds_budget)
+  int32_t rectify_budget = FVO_RECTIFY_LDS_BYTES;
 };
 
 // Error helpers: set ctx->err and return negative status.
@@ -234,6 +236,21 @@ int dense_append_run(fvo_ctx* ctx, const int16_t* disp, int batch, int H, int W,
 // cv2.reprojectImageTo3D (dense.hip).  min_key: [batch] u32, used with handle_missing only.
 int reproject_run(fvo_ctx* ctx, const void* disp, int is_f32, int batch, int H, int W, int64_t image_stride,
                   int pitch, const double* Q, int handle_missing, uint32_t* min_key, float* out, hipStream_t s);
+// Stereo rectification (rectify.hip).  capi_rectify.cpp validates the calibration and hands the
+// launchers this: ir = inverse(newK * R) by the 3x3 closed form, the camera's own fx, fy, cx, cy
+// and the radial-tangential coefficients (rational: n_dist == 8, else k4..k6 = 0 and the
+// denominator, exactly 1, is dropped).
+struct RectifyLens {
+  double ir[9];
+  double fx, fy, u0, v0;
+  double k1, k2, p1, p2, k3, k4, k5, k6;
+  int rational;
+};
+int rectify_map_run(fvo_ctx* ctx, const RectifyLens& L, int16_t* map1, uint16_t* map2, hipStream_t s);
+int remap_run(fvo_ctx* ctx, const uint8_t* src, int batch, int64_t sstride, int spitch, int channels,
+              const int16_t* map1, const uint16_t* map2, uint8_t* dst, int64_t dstride, int dpitch, hipStream_t s);
+int rectify_gray_run(fvo_ctx* ctx, const uint8_t* src, int batch, int64_t sstride, int spitch, int channels,
+                     const RectifyLens& L, uint8_t* gray, int64_t dstride, int dpitch, hipStream_t s);
 int mono_init(fvo_ctx* ctx);
 int gather_run(fvo_ctx* ctx, const float* kp0, const float* kp1, const int32_t* matches, const int32_t* nmatch,
                int batch, int cap, float* p0, float* p1, int32_t* npts, hipStream_t s);

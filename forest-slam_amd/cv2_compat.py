@@ -10,7 +10,8 @@ Face 1 mirrors the OpenCV calls of ros_ws/src/stereo_slam.py:
        for Lowe's ratio test)
     StereoSGBM_create(...).compute(L, R)                        (:108-117)
       (with OpenCV's speckleWindowSize / speckleRange post-filter, filterSpeckles itself, and
-       their usual partner reprojectImageTo3D(disparity, Q))
+       their usual partner reprojectImageTo3D(disparity, Q), and -- for a rig that is not row-aligned
+       as the reference's nearly is -- stereoRectify, initUndistortRectifyMap and remap)
     ok, rvec, tvec, inliers = solvePnPRansac(P, p, K, dist, ...)  (:294-295)
     R, _ = Rodrigues(rvec)                                      (:298)
 and of ros_ws/src/mono_slam.py:
@@ -411,6 +412,78 @@ def reprojectImageTo3D(disparity, Q, handleMissingValues=False, ddepth=-1):
     out = ctx.reproject_to_3d(t.to(dev), Qm, bool(handleMissingValues))
     if t.dim() == 2:
         out = out[0]
+    return out.cpu().numpy() if is_np else out
+
+
+# --------------------------------------------------------------------------- stereo rectification
+CV_16SC2 = 11
+INTER_LINEAR = 1
+BORDER_CONSTANT = 0
+CALIB_ZERO_DISPARITY = 1024
+_rectify_cache = _CtxCache()
+
+
+def _rectify_ctx(width, height):
+    dev = _device()
+    return _rectify_cache.get((dev.index, int(width), int(height)),
+                              lambda: _lib.Context(int(width), int(height), max_batch=1, stages=_lib.STAGE_BF,
+                                                   kp_capacity=64))
+
+
+def stereoRectify(cameraMatrix1, distCoeffs1, cameraMatrix2, distCoeffs2, imageSize, R, T, R1=None, R2=None, P1=None,
+                  P2=None, Q=None, flags=CALIB_ZERO_DISPARITY, alpha=-1, newImageSize=(0, 0)):
+    """cv2.stereoRectify -> (R1, R2, P1, P2, Q, validPixROI1, validPixROI2): rectify.stereo_rectify
+    (host float64; OpenCV parity is restated and property-checked, not pinned).  flags 0 or
+    CALIB_ZERO_DISPARITY, alpha -1 or in [0, 1], newImageSize (0, 0) only."""
+    from . import rectify
+    return rectify.stereo_rectify(cameraMatrix1, distCoeffs1, cameraMatrix2, distCoeffs2, imageSize, R, T, flags=flags,
+                                  alpha=alpha, newImageSize=newImageSize).cv2_tuple()
+
+
+def initUndistortRectifyMap(cameraMatrix, distCoeffs, R, newCameraMatrix, size, m1type):
+    """cv2.initUndistortRectifyMap(K, dist, R, P, (W, H), cv2.CV_16SC2) -> (map1 int16 (H, W, 2),
+    map2 uint16 (H, W)) on the GPU (fvo_rectify_map).  R None = identity; newCameraMatrix None = K,
+    3x3 or 3x4 (a projection matrix: its left 3x3 is used).  Only m1type CV_16SC2 and 4, 5 or 8
+    distortion coefficients are implemented."""
+    if m1type != CV_16SC2:
+        raise NotImplementedError("initUndistortRectifyMap: only m1type=CV_16SC2 is implemented")
+    d = np.zeros(5) if distCoeffs is None else np.asarray(distCoeffs, np.float64).reshape(-1)
+    if d.size not in (4, 5, 8):
+        raise NotImplementedError("initUndistortRectifyMap: only 4, 5 or 8 distortion coefficients are implemented")
+    P = None if newCameraMatrix is None else np.asarray(newCameraMatrix, np.float64)
+    if P is not None:
+        if P.shape not in ((3, 3), (3, 4)):
+            raise error("initUndistortRectifyMap: newCameraMatrix must be 3x3 or 3x4")
+        P = np.ascontiguousarray(P[:, :3])
+    Rm = None if R is None else np.asarray(R, np.float64)
+    if Rm is not None and Rm.shape != (3, 3):
+        raise NotImplementedError("initUndistortRectifyMap: R must be a 3x3 matrix")
+    m1, m2 = _rectify_ctx(size[0], size[1]).rectify_map(cameraMatrix, d, Rm, P)
+    return m1.cpu().numpy(), m2.cpu().numpy()
+
+
+def remap(src, map1, map2, interpolation, dst=None, borderMode=BORDER_CONSTANT, borderValue=0):
+    """cv2.remap(src, map1, map2, cv2.INTER_LINEAR) on the GPU (fvo_remap_u8): u8 images of 1 or 3
+    channels with a CV_16SC2 + CV_16UC1 fixed-point map of the image's own size.  Only
+    INTER_LINEAR with BORDER_CONSTANT and borderValue 0 are implemented."""
+    if interpolation != INTER_LINEAR or borderMode != BORDER_CONSTANT or np.any(np.asarray(borderValue) != 0):
+        raise NotImplementedError("remap: only INTER_LINEAR with BORDER_CONSTANT 0 is implemented")
+    if dst is not None:
+        raise NotImplementedError("remap: dst is not implemented")
+    is_np = not isinstance(src, torch.Tensor)
+    t = torch.from_numpy(np.ascontiguousarray(src)) if is_np else src
+    m1 = map1 if isinstance(map1, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(map1))
+    m2 = map2 if isinstance(map2, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(map2))
+    if m1.dtype != torch.int16 or m1.dim() != 3 or m1.shape[2] != 2 or m2.dtype != torch.uint16 or m2.dim() != 2:
+        raise NotImplementedError("remap: only CV_16SC2 + CV_16UC1 maps are implemented")
+    if t.dtype != torch.uint8 or t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[2] not in (1, 3)):
+        raise NotImplementedError("remap: only 8-bit images of 1 or 3 channels are implemented")
+    H, W = t.shape[:2]
+    if tuple(m1.shape[:2]) != (H, W) or tuple(m2.shape) != (H, W):
+        raise NotImplementedError("remap: the map must have the image's size")
+    dev = _device()
+    src4 = t.to(dev).contiguous().reshape(1, H, W, -1)
+    out = _rectify_ctx(W, H).remap(src4, m1.to(dev).contiguous(), m2.to(dev).contiguous()).reshape(t.shape)
     return out.cpu().numpy() if is_np else out
 
 

@@ -72,7 +72,7 @@ def _upload(msgs, dev):
 def run_stereo_bag(path: str, batch: int = 32, nfeatures: int = 500, frame_interval: int = 1, ba_window: int = 0,
                    device="cuda:0", K_left=K0, dist_left=DIST_L, K_right=K1, dist_right=DIST_R, baseline=BASELINE,
                    point_map=None, speckle_window: int = 0, speckle_range: int = 0, match_ratio: float = 0.0,
-                   dense_map=None, dense_step: int = 4, dense_z_max: float = 1000.0):
+                   dense_map=None, dense_step: int = 4, dense_z_max: float = 1000.0, rectify=None):
     """stereo_slam.py's ORB branch over a bag -> (TUM rows f64[n,8], relative T, statuses).
     match_ratio: > 0 keeps only the cross-checked matches that pass Lowe's ratio test at that
     ratio (0 = the reference's matcher).
@@ -82,21 +82,40 @@ def run_stereo_bag(path: str, batch: int = 32, nfeatures: int = 500, frame_inter
     frame (stereo_slam.py:308-318).
     dense_map: a ``mapping.PointMap`` that receives every posed frame's disparity map as a point
     cloud (every dense_step-th pixel of every dense_step-th row with a valid disparity and
-    0.1 < Z < dense_z_max), placed by the same poses and frame mask as point_map's sparse points."""
+    0.1 < Z < dense_z_max), placed by the same poses and frame mask as point_map's sparse points.
+    rectify: None = the reference's ingest (each camera undistorted with its own K: the rig must
+    be row-aligned already), or the rig's extrinsic (R, T), x_right = R x_left + T: the pair is
+    rectified (rectify.stereo_rectify once, then fvo_rectify_gray with R1 / P1 and R2 / P2 per
+    camera; bgr8 and mono8 images), the front end runs with the rectified camera matrix, zero
+    distortion and the rectified baseline (the `baseline` argument is not used), and the poses
+    are those of the RECTIFIED left camera: x_rect = R1 x_left."""
     bag = rosbag.Bag(path)
     pairs = select_stereo_pairs(bag, frame_interval)
     if len(pairs) < 2:
         return np.zeros((0, 8)), np.zeros((0, 4, 4)), np.zeros((0,), np.int32)
     H, W = pairs[0][1].height, pairs[0][1].width
-    fe = vo.StereoFrontEnd(W, H, K_left, dist_left, baseline, batch=batch, nfeatures=nfeatures, device=device,
-                           ba_window=ba_window, speckle_window=speckle_window, speckle_range=speckle_range,
-                           match_ratio=match_ratio)
+    rect = None
+    if rectify is not None:
+        from .rectify import stereo_rectify
+        rect = stereo_rectify(K_left, dist_left, K_right, dist_right, (W, H), rectify[0], rectify[1])
+        if rect.idx != 0:
+            raise ValueError("run_stereo_bag: a vertical rig cannot go on to SGBM")
+        if not rect.P2[0, 3] < 0:
+            raise ValueError("run_stereo_bag: the second camera is to the left of the first (R2 T has a positive x): "
+                             "disparities would be negative; pass the cameras in left, right order")
+    fe = vo.StereoFrontEnd(W, H, K_left if rect is None else rect.K_rect, dist_left if rect is None else np.zeros(5),
+                           baseline if rect is None else rect.baseline, batch=batch, nfeatures=nfeatures,
+                           device=device, ba_window=ba_window, speckle_window=speckle_window,
+                           speckle_range=speckle_range, match_ratio=match_ratio)
     ctx, dev = fe.ctx, fe.dev
 
     def gray(lo, hi):
-        L = ctx.undistort_gray(_upload([p[1] for p in pairs[lo:hi]], dev), K_left, dist_left)
-        R = ctx.undistort_gray(_upload([p[2] for p in pairs[lo:hi]], dev), K_right, dist_right)
-        return L, R
+        left, right = _upload([p[1] for p in pairs[lo:hi]], dev), _upload([p[2] for p in pairs[lo:hi]], dev)
+        if rect is None:
+            return ctx.undistort_gray(left, K_left, dist_left), ctx.undistort_gray(right, K_right, dist_right)
+        ch = 1 if left.dim() == 3 else 3  # mono8 [B,H,W] or bgr8 [B,H,W,3]
+        return (ctx.rectify_gray(left, K_left, dist_left, rect.R1, rect.P1[:, :3], channels=ch),
+                ctx.rectify_gray(right, K_right, dist_right, rect.R2, rect.P2[:, :3], channels=ch))
 
     L0, R0 = gray(0, 1)
     fe.prime(L0[0], R0[0])

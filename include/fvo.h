@@ -42,6 +42,10 @@
  *                              back-projection of stereo_slam.py:262-289 at every step-th pixel + the
  *                              map update of :308-318, no reference counterpart
  *   fvo_reproject_to_3d     <- cv2.reprojectImageTo3D(disparity, Q, handleMissingValues)
+ *   fvo_rectify_map         <- cv2.initUndistortRectifyMap(K, dist, R, P, size, cv2.CV_16SC2)
+ *   fvo_remap_u8            <- cv2.remap(img, map1, map2, cv2.INTER_LINEAR)
+ *   fvo_rectify_gray        <- both fused + cv2.cvtColor(., COLOR_BGR2GRAY): the rectifying ingest
+ *                              (no reference counterpart: the reference does not rectify)
  *
  * Conventions
  *  - All array pointers are DEVICE pointers owned by the caller (e.g. torch tensors'
@@ -300,6 +304,52 @@ int fvo_recover_pose(fvo_ctx* ctx, const double* E, const int32_t* e_status, con
 int fvo_undistort_gray(fvo_ctx* ctx, const uint8_t* bgr, int32_t batch, int64_t src_stride, int32_t src_pitch,
                        const double* K, const double* dist, uint8_t* gray, int64_t dst_stride, int32_t dst_pitch,
                        fvo_stream stream);
+
+/* Stereo rectification (any stage; no workspace; image size = the context's width x height;
+ * asynchronous and graph-capturable like every hot call).  Conventions of fvo_undistort_gray's
+ * map: fp64, the column term evaluated directly, iu = cvRound(u*32), (short)(iu >> 5),
+ * frac = (iv & 31)*32 + (iu & 31); no stripes and no cy shift (those are cv2.undistort's).
+ *
+ * fvo_rectify_map   <- cv2.initUndistortRectifyMap(K, dist, R, newK, (width, height), CV_16SC2)
+ *   K, R, newK: host double[9] row-major; R NULL = identity, newK NULL = K (for a 3x4 projection
+ *   matrix pass its left 3x3).  dist: host double[n_dist], n_dist 4 (k1 k2 p1 p2), 5 (+ k3) or
+ *   8 (+ k4 k5 k6, the rational model).  Refused: non-finite entries, det(newK*R) == 0, and a
+ *   view whose ray denominator _w = ir[6]*col + ir[7]*row + ir[8] (ir = inverse(newK*R)) is not
+ *   > 0 (with a finite reciprocal) at every image corner.
+ *   map1: device int16 [height][width][2] (x, y), 4-byte aligned; map2: device uint16
+ *   [height][width].
+ * fvo_remap_u8      <- cv2.remap(src, map1, map2, INTER_LINEAR, BORDER_CONSTANT, 0) on `batch` u8
+ *   images of `channels` (1 or 3) interleaved channels; dst has the same channel count.  Any
+ *   int16 map values are safe (taps outside the image read 0); map2 is read as map2 & 1023.
+ *   dst must not overlap src (refused; likewise gray and src of fvo_rectify_gray).
+ * fvo_rectify_gray  <- both of the above fused, no map stored, then cv2.cvtColor(., BGR2GRAY)
+ *   when channels == 3 (a mono8 image is only remapped): the rectifying ingest.  Its bytes equal
+ *   fvo_rectify_map -> fvo_remap_u8 -> the 14-bit gray conversion.
+ * src: image b at src + b*src_stride, rows src_pitch (>= channels*width) bytes apart; dst
+ * likewise (dst_pitch >= channels*width), gray with dst_pitch >= width.
+ *
+ * Kernel shape: a block makes one FVO_RECTIFY_TILE_W x FVO_RECTIFY_TILE_H output tile.  With
+ * [x0, x1] x [y0, y1] the bounds of the tile's integer map entries, bw = x1 - x0 + 2 and
+ * bh = y1 - y0 + 2, the block stages that source box in LDS iff
+ *   ((bw*channels + 6) & ~3) * bh <= FVO_RECTIFY_LDS_BYTES
+ * and gathers its taps from global memory otherwise; both paths produce the same bytes. */
+#define FVO_RECTIFY_TILE_W 64
+#define FVO_RECTIFY_TILE_H 16
+#define FVO_RECTIFY_LDS_BYTES 8192
+int fvo_rectify_map(fvo_ctx* ctx, const double* K, const double* dist, int32_t n_dist, const double* R,
+                    const double* newK, int16_t* map1, uint16_t* map2, fvo_stream stream);
+int fvo_remap_u8(fvo_ctx* ctx, const uint8_t* src, int32_t batch, int64_t src_stride, int32_t src_pitch,
+                 int32_t channels, const int16_t* map1, const uint16_t* map2, uint8_t* dst, int64_t dst_stride,
+                 int32_t dst_pitch, fvo_stream stream);
+int fvo_rectify_gray(fvo_ctx* ctx, const uint8_t* src, int32_t batch, int64_t src_stride, int32_t src_pitch,
+                     int32_t channels, const double* K, const double* dist, int32_t n_dist, const double* R,
+                     const double* newK, uint8_t* gray, int64_t dst_stride, int32_t dst_pitch, fvo_stream stream);
+/* Measurement / test hook, NOT for production use: the staging budget of this context's later
+ * fvo_remap_u8 and fvo_rectify_gray launches, in [0, FVO_RECTIFY_LDS_BYTES] (0 = every block
+ * gathers directly; the default, FVO_RECTIFY_LDS_BYTES, is the measured faster choice).  It exists
+ * so that tools/bench_rectify.py can time both paths and the tests can run both on one input; the
+ * value stays on the context until set again.  The output bytes do not depend on it. */
+int fvo_rectify_lds_budget(fvo_ctx* ctx, int32_t bytes);
 
 /* Motion-blur ablation on `batch` gray images (any stage; no workspace), image size = the
  * context's width x height:  out = np.where(mask, cv2.filter2D(img, -1, diag(ones(k))/k), img)
