@@ -657,7 +657,8 @@ int fvo_timing_read(fvo_ctx* c, double* ms, int32_t* launches) {
 // which: 0 pyramid, 1 blurred pyramid, 2 FAST score map (all [max_batch][total_px] u8),
 //        3 per-level candidate counts, 4 after retainBest(2n), 5 after retainBest(n) (i32 [B][L]),
 //        6 PnP RANSAC inlier count per iteration (i32 [B][1000]), 7 PnP hypotheses (f64 [B][1000][6]),
-//        8 PnP RANSAC state (i32 [B][4]: best inlier count, iteration bound, best iteration, points).
+//        8 PnP RANSAC state (i32 [B][4]: best inlier count, iteration bound, best iteration, points),
+//        9 SGBM control words, 10 no buffer (0 bytes): ORB orientation as a separate pass from now on.
 int fvo_debug_buffer(fvo_ctx* c, int which, void** ptr, int64_t* bytes) {
   if (!c || !ptr || !bytes) return -1;
   const int64_t B = c->cfg.max_batch;
@@ -680,6 +681,12 @@ int fvo_debug_buffer(fvo_ctx* c, int which, void** ptr, int64_t* bytes) {
     case 9:  // SGBM control words: ticket, generation, hand-off timeouts, per-pair failure flags
       if (!c->sg_ctl) return fvo_fail(c, "no SGBM workspace");
       *ptr = c->sg_ctl; *bytes = (4 + B) * 4; return 0;
+    case 10:  // no buffer: a switch, so that tests and tools/bench_orb.py can run the ORB path that
+              // no accepted configuration selects (orb_init) -- from the next call on this context
+              // forms the orientation in a pass of its own (k_angle) instead of inside k_brief
+      if (!c->pyr) return fvo_fail(c, "orb stage not enabled");
+      c->g.angle_pass = true;
+      *ptr = nullptr; *bytes = 0; return 0;
     default: return fvo_fail(c, "unknown debug buffer");
   }
 }

@@ -24,6 +24,7 @@ struct OrbGeom {
   int64_t total_px;
   int total_rows;
   int64_t cand_total;
+  bool angle_pass;                      // orientation as a pass of its own (k_angle), not inside k_brief
 };
 
 // Constant tables for the INTER_LINEAR_EXACT pyramid resize (per level, per axis).

@@ -3,7 +3,8 @@
 //
 // Stages (one launch each, all images of the batch at once):
 //   pyramid      level 0 copy + 7 INTER_LINEAR_EXACT downscales (ufixedpoint16 weights)
-//   fast_score   FAST-9/16 corner test + cornerScore<16> -> u8 score map (all levels)
+//   fast_score   FAST-9/16 corner test + cornerScore<16> -> u8 score map (all levels; only
+//                the tiles that cover a level's interior, edgeThreshold px inside its sides)
 //   nms_count    3x3 strict-max NMS + 31-px border filter, per-row counts
 //   row_scan     per-level exclusive scan of row counts
 //   nms_compact  ordered (row-major) compaction -> packed candidates (score<<24|y<<12|x)
@@ -12,7 +13,8 @@
 //   harris       7x7 Harris response per candidate (wave per keypoint)
 //   select       retainBest(n_l) on the Harris responses
 //   finalize     per-image level offsets / counts
-//   angle        intensity-centroid angle (fastAtan2) + keypoint records
+//   angle        intensity-centroid angle (fastAtan2) + keypoint records (inside brief, from
+//                the patch it stages; a launch of its own only where orb_init says so)
 //   blur         GaussianBlur 7x7 sigma 2 (8-bit fixed-point separable, REFLECT_101)
 //   brief        steered rBRIEF, one wave per keypoint, 4 ballots = 32 bytes
 // All float expressions are evaluated in the order OpenCV writes them; the library is
@@ -37,7 +39,7 @@ struct OrbDev {
   float scale[FVO_MAX_LEVELS];
   int nfeat[FVO_MAX_LEVELS];
   int tile0[FVO_MAX_LEVELS + 1];  // first 64x32 FAST tile of each level (per image)
-  int ntx[FVO_MAX_LEVELS];        // tiles per row of each level
+  int ntx[FVO_MAX_LEVELS];        // tiles per row of each level (0: the level has no tiles)
   int btile0[FVO_MAX_LEVELS + 1]; // first 256x32 blur tile of each level (per image)
   int bntx[FVO_MAX_LEVELS];       // blur tiles per row of each level
 };
@@ -160,7 +162,14 @@ __constant__ int c_cdx[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2,
 __constant__ int c_cdy[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
 
 // ------------------------------------------------------------------ FAST + NMS (tiled)
-// One block per 64 x 32 tile of a level: the image patch (tile + 4-px apron) is staged in
+// The tiles of a level start at (org, org) and cover (w - 2 org) x (h - 2 org); a level that
+// leaves nothing has no tiles (make_dev).  The hot path lays them with org = edgeThreshold:
+// the keep step below drops every pixel nearer than that to the level's sides and
+// compact_level reads no other rows, so the scores that can reach a kept pixel -- the
+// interior and the 1-px NMS halo every tile carries -- are all still computed, and the tiles
+// that only ever fed the border filter are not launched.  The SCOREMAP instance is launched
+// with org = 0 (whole levels).
+// One block per 64 x 32 tile: the image patch (tile + 4-px apron) is staged in
 // LDS; the FAST test runs on the tile + 1-px halo, the positions that pass are packed into
 // an LDS list so cornerScore<16> runs on dense lanes (textured frames make ~80 % of waves
 // contain a corner, so per-pixel scoring ran the score code on nearly every wave); then the
@@ -223,7 +232,7 @@ __device__ __forceinline__ int tile_level(const OrbDev& G, int t) {
 template <bool SCOREMAP>
 __global__ __launch_bounds__(kFT) void k_fast_nms(const OrbDev G, const uint8_t* __restrict__ pyr,
                                                   uint8_t* __restrict__ score, uint8_t* __restrict__ trec,
-                                                  int64_t total, int thr, int edge, int ntiles) {
+                                                  int64_t total, int thr, int edge, int org, int ntiles) {
   __shared__ __attribute__((aligned(16))) uint8_t s_img[kIH][kIW];
   __shared__ __attribute__((aligned(16))) uint8_t s_sc[kFH][kFW];
   __shared__ uint16_t s_list[kFH * kFW];
@@ -238,12 +247,17 @@ __global__ __launch_bounds__(kFT) void k_fast_nms(const OrbDev G, const uint8_t*
   const int l = tile_level(G, t);
   const int lt = t - G.tile0[l];
   const int tx = lt % G.ntx[l], ty = lt / G.ntx[l];
-  const int x0 = tx * kTW, y0 = ty * kTH;
+  const int x0 = org + tx * kTW, y0 = org + ty * kTH;
   const int w = G.w[l], h = G.h[l];
   const uint8_t* im = pyr + b * total + G.off[l];
   if (x0 >= 8 && x0 + kTW + 12 <= w && y0 >= 4 && y0 + kTH + 4 <= h) {
     // interior tile: the staged rows and the aligned dwords around them lie inside the level
-    // row, so a row's 76 bytes come from 20 aligned dwords, byte-aligned by v_alignbyte
+    // row, so a row's 76 bytes come from 20 aligned dwords, byte-aligned by v_alignbyte.  The
+    // test is on the tile's own x0, y0, whatever origin they come from: a staged row is bytes
+    // [x0 - 5, x0 + 71) of a level row, and rounding its dwords' addresses down to 4 and
+    // reading 8 bytes touches at most [x0 - 8, x0 + 75) -- inside [0, w) of that same row.
+    // From an origin of 8 or more (edgeThreshold is at least 15) that is every tile but the
+    // last column's and the last row's.
     for (int i = threadIdx.x; i < kIH * (kIW / 4); i += kFT) {
       const int r = i / (kIW / 4), k = i % (kIW / 4);
       const uint8_t* p = im + (int64_t)(y0 - 4 + r) * w + x0 - 1 - kIC + 4 * k;
@@ -677,7 +691,9 @@ __device__ int select_block(SelShared& sh, typename E::T* a, int n, int keep, I*
 }
 
 // Ordered (row-major) compaction of level l's kept pixels from the tile records k_fast_nms
-// wrote: (row, tile) keep words in row-major order, a thread per run of up to kCmpPer
+// wrote (tiles from (edge, edge), so level row y is row (y - edge) % kTH of tile row
+// (y - edge) / kTH and bit k of tile tx is x = edge + kTW tx + k): (row, tile) keep words in
+// row-major order, a thread per run of up to kCmpPer
 // consecutive words (all loads in flight at once), one block scan of the runs' counts, each
 // word's pixels written at its offset -- (score << 24 | y << 12 | x), the order cv::FAST lists
 // keypoints in.  Candidates go to the global array and, while they fit, to the LDS copy.
@@ -688,7 +704,7 @@ __device__ int compact_level(SelShared& sh, const OrbDev& G, const uint8_t* __re
                              int l, int b, uint32_t* __restrict__ out, uint32_t* s_out) {
   const int h = G.h[l], ntx = G.ntx[l];
   const int ya = edge, yb = h - edge;  // the NMS border filter keeps nothing outside
-  const int npairs = yb > ya ? (yb - ya) * ntx : 0;
+  const int npairs = yb > ya ? (yb - ya) * ntx : 0;  // ntx = 0: a level without interior
   const uint8_t* lrec = trec + ((int64_t)b * ntiles + G.tile0[l]) * kTRec;
   if (threadIdx.x == 0) { sh.carry[0] = 0; sh.carry[1] = 0; }
   __syncthreads();
@@ -703,8 +719,8 @@ __device__ int compact_level(SelShared& sh, const OrbDev& G, const uint8_t* __re
     for (int j = 0, y = y0, tx = tx0; j < kCmpPer; ++j) {
       w[j] = 0;
       if (q0 + j < q1)
-        w[j] = reinterpret_cast<const unsigned long long*>(lrec + (int64_t)((y / kTH) * ntx + tx) * kTRec +
-                                                           kRecKeep)[y % kTH];
+        w[j] = reinterpret_cast<const unsigned long long*>(lrec + (int64_t)(((y - edge) / kTH) * ntx + tx) * kTRec +
+                                                           kRecKeep)[(y - edge) % kTH];
       cnt += __popcll(w[j]);
       if (++tx == ntx) { tx = 0; ++y; }
     }
@@ -714,12 +730,12 @@ __device__ int compact_level(SelShared& sh, const OrbDev& G, const uint8_t* __re
     for (int j = 0, y = y0, tx = tx0; j < kCmpPer; ++j) {
       unsigned long long word = w[j];
       if (word) {
-        const uint8_t* rec = lrec + (int64_t)((y / kTH) * ntx + tx) * kTRec;
-        const uint8_t* sc = rec + kRecSc + reinterpret_cast<const uint16_t*>(rec + kRecPre)[y % kTH];
+        const uint8_t* rec = lrec + (int64_t)(((y - edge) / kTH) * ntx + tx) * kTRec;
+        const uint8_t* sc = rec + kRecSc + reinterpret_cast<const uint16_t*>(rec + kRecPre)[(y - edge) % kTH];
         for (int k = 0; word; ++k) {
           const int bit = __builtin_ctzll(word);
           word &= word - 1ull;
-          const uint32_t e = ((uint32_t)sc[k] << 24) | ((uint32_t)y << 12) | (uint32_t)(64 * tx + bit);
+          const uint32_t e = ((uint32_t)sc[k] << 24) | ((uint32_t)y << 12) | (uint32_t)(edge + kTW * tx + bit);
           out[o] = e;
           if (o < CAP) s_out[o] = e;
           ++o;
@@ -989,32 +1005,85 @@ __global__ __launch_bounds__(256) void k_blur(const OrbDev G, const uint8_t* __r
 constexpr int kBrR = 19, kBrP = 2 * kBrR + 1, kBrS = kBrP + 6;  // sample radius, blurred / source side
 constexpr int kBrSW = kBrS + 3, kBrPW = kBrP + 1;                // LDS row pitches
 
-__global__ __launch_bounds__(256, 4) void k_brief(const OrbDev G, const uint8_t* __restrict__ pyr,
-                                               const float* __restrict__ kp, const int32_t* __restrict__ counts,
-                                               uint8_t* __restrict__ desc, int64_t total, int cap) {
+// ANGLE: the same wave also does k_angle's work, from the patch it has staged anyway -- the
+// orientation disc (radius patch / 2 = 15) lies inside the staged square (radius 22) and its
+// moments are integer sums, the same in any order.  Keypoint j of the image is element
+// j - koff[l] of level l's Harris-selected records; the patch is staged around the record's
+// integer (x, y) (the centre the other instance recovers as rint(x s (1 / s)) is that integer:
+// the two roundings move x s (1 / s) by under 1e-3 for x < 4096).  Two half-waves of 32
+// columns take the disc's rows 0 .. -15 and 1 .. 15, lane 0 writes the keypoint record exactly
+// as k_angle does and the angle goes on to the rotation.  orb_init says when this instance may
+// run (OrbGeom::angle_pass); otherwise k_angle runs first and the plain instance reads its
+// records.
+constexpr int kAngR = 15;  // largest orientation radius the ANGLE instance covers (31 columns of a half-wave)
+static_assert(kAngR <= kBrR + 3 && 2 * kAngR + 1 <= 32, "orientation disc inside the staged patch, a column per lane");
+
+// Registers: the ANGLE instance is held to 5 waves per SIMD (<= 102 VGPRs; it takes 96 and spills
+// 14), which measured faster than the 125 registers and 4 waves it takes unbounded; the plain
+// instance fits 95 on its own.
+template <bool ANGLE>
+__global__ __launch_bounds__(256, ANGLE ? 5 : 4) void k_brief(const OrbDev G, const uint8_t* __restrict__ pyr,
+                                               const uint64_t* __restrict__ hel, const int32_t* __restrict__ koff,
+                                               float* __restrict__ kp, const int32_t* __restrict__ counts,
+                                               uint8_t* __restrict__ desc, int64_t total, int64_t cand_total,
+                                               int nlevels, int cap, int patch) {
   __shared__ __attribute__((aligned(16))) uint8_t s_src[4][kBrS][kBrSW];
   __shared__ uint8_t s_blr[4][kBrP][kBrPW];
   const XcdBlock xb = xcd_block();  // one image's blocks on one XCD: overlapping patches in one L2
   const int b = xb.y;
   const int n = counts[b];
-  if (n < 0) return;
-  const int wpb = blockDim.x >> 6, lane = wave_lane(), wv = threadIdx.x >> 6;
+  // more keypoints than the caller's capacity (n < 0): no descriptors; the first cap records are
+  // still written, as k_angle writes them
+  if (n < 0 && !ANGLE) return;
+  const int nk = n < 0 ? cap : n;
+  // wv as a scalar: the keypoint index, its level and every address derived from them are then
+  // wave-uniform to the compiler (scalar registers and loads)
+  const int wpb = blockDim.x >> 6, lane = wave_lane(), wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   uint8_t(*src)[kBrSW] = s_src[wv];
   uint8_t(*blr)[kBrPW] = s_blr[wv];
-  for (int j = xb.x * wpb + wv; j < n; j += gridDim.x * wpb) {
-    const float* k = kp + ((int64_t)b * cap + j) * FVO_KP_STRIDE;
-    const int l = (int)k[5];
-    const float scale = 1.f / G.scale[l];
-    float angle = k[3];
-    angle *= (float)(3.14159265358979323846 / 180.f);
-    const float a = (float)cos((double)angle), bb = (float)sin((double)angle);
-    const int cy = (int)rintf(k[1] * scale), cx = (int)rintf(k[0] * scale);
+  // ANGLE: the image's level offsets are read once, and keypoint j's record is fetched while
+  // keypoint j - stride is worked on, so the patch loads are a keypoint's only dependent round trip
+  int ko[FVO_MAX_LEVELS];
+  int l_nx = 0;
+  uint64_t e_nx = 0;
+  auto fetch = [&](int jj) {
+    int kb = 0;
+    l_nx = 0;
+#pragma unroll
+    for (int q = 1; q < FVO_MAX_LEVELS; ++q)
+      if (jj >= ko[q]) { l_nx = q; kb = ko[q]; }
+    e_nx = hel[b * cand_total + G.cand_off[l_nx] + (jj - kb)];
+  };
+  const int j0 = xb.x * wpb + wv, stride = gridDim.x * wpb;
+  if (ANGLE) {
+#pragma unroll
+    for (int q = 0; q < FVO_MAX_LEVELS; ++q) ko[q] = q < nlevels ? koff[b * (nlevels + 1) + q] : 0x7fffffff;
+    if (j0 < nk) fetch(j0);
+  }
+  for (int j = j0; j < nk; j += stride) {
+    float* k = kp + ((int64_t)b * cap + j) * FVO_KP_STRIDE;
+    int l, cx, cy;
+    float angle, resp;
+    if (ANGLE) {
+      l = l_nx;
+      const uint64_t e = e_nx;
+      if (j + stride < nk) fetch(j + stride);
+      cx = (int)(e & 0xFFF);
+      cy = (int)((e >> 12) & 0xFFF);
+      resp = __uint_as_float((uint32_t)(e >> 32));
+    } else {
+      l = (int)k[5];
+      const float scale = 1.f / G.scale[l];
+      angle = k[3];
+      cy = (int)rintf(k[1] * scale);
+      cx = (int)rintf(k[0] * scale);
+    }
     const int w = G.w[l], h = G.h[l];
     const uint8_t* im = pyr + b * total + G.off[l];
     const int sx0 = cx - kBrR - 3, sy0 = cy - kBrR - 3;
     if (sx0 >= 0 && sy0 >= 0 && sx0 + kBrS <= w && sy0 + kBrS <= h) {
-      // the usual case (keypoints lie edgeThreshold >= 31 px inside their level, the patch
-      // reaches 22): no border handling, each row's 48 bytes as 12 dwords from aligned loads
+      // the usual case (every keypoint of an edgeThreshold >= 22, the default 31 among them: the
+      // patch reaches 22): no border handling, each row's 48 bytes as 12 dwords from aligned loads
       // (v_alignbyte), all 9 of a lane's loads in flight together
       constexpr int kRW = kBrSW / 4, kN = kBrS * kRW, kIt = (kN + 63) / 64;
       const uint8_t* p0 = im + (int64_t)sy0 * w + sx0;
@@ -1029,7 +1098,9 @@ __global__ __launch_bounds__(256, 4) void k_brief(const OrbDev G, const uint8_t*
       }
     } else {
       // a patch crossing the level's border (REFLECT_101 per byte): not reached by keypoints
-      // of the default edgeThreshold, kept small in registers
+      // of the default edgeThreshold, kept small in registers.  Only positions outside the level
+      // are mirrored, so with edgeThreshold >= patch / 2 (orb_init) the orientation disc of the
+      // ANGLE instance still reads true pixels here
       constexpr int kBrN = kBrS * kBrS;
 #pragma unroll 1
       for (int i = lane; i < kBrN; i += 64) {
@@ -1041,6 +1112,45 @@ __global__ __launch_bounds__(256, 4) void k_brief(const OrbDev G, const uint8_t*
     }
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_wave_barrier();
+    if (ANGLE) {
+      // intensity-centroid moments of the disc, centre at src[kBrR + 3][kBrR + 3]: every byte
+      // read unconditionally (-15 <= u <= 16, |v| <= 15 stay inside the square) and masked by the
+      // circle afterwards, c_umax[t] a scalar
+      const int half = patch / 2;
+      const int u = (lane & 31) - half;
+      const bool up = lane >= 32;  // rows 1 .. half; the other half-wave rows 0 .. -half
+      int m10 = 0, m01 = 0;
+#pragma unroll
+      for (int t = 0; t <= kAngR; ++t) {
+        const int v = up ? t : -t;
+        const int p = src[kBrR + 3 + v][kBrR + 3 + min(u, kAngR + 1)];
+        const int d = c_umax[t];
+        if (t <= half && u >= -d && u <= d && !(up && t == 0)) {
+          m10 += u * p;
+          m01 += v * p;
+        }
+      }
+      m10 = wave_sum(m10);
+      m01 = wave_sum(m01);
+      angle = fast_atan2_deg((float)m01, (float)m10);
+      if (lane == 0) {
+        const float s = G.scale[l];
+        k[0] = (float)cx * s;
+        k[1] = (float)cy * s;
+        k[2] = patch * s;
+        k[3] = angle;
+        k[4] = resp;
+        k[5] = (float)l;
+        k[6] = -1.f;
+        k[7] = 0.f;
+      }
+      if (n < 0) {
+        __builtin_amdgcn_wave_barrier();  // the next keypoint overwrites this wave's patch
+        continue;
+      }
+    }
+    angle *= (float)(3.14159265358979323846 / 180.f);
+    const float a = (float)cos((double)angle), bb = (float)sin((double)angle);
     if (lane < kBrP) {
       const int c = lane;
       // vertical 7 taps from a 7-row ring: rows in groups of 7 (ring slot = row % 7, static
@@ -1103,7 +1213,7 @@ static int cv_round_f(float v) { return (int)lrintf(v); }
 }  // namespace
 
 namespace {
-OrbDev make_dev(const OrbGeom& g);
+OrbDev make_dev(const OrbGeom& g, int org);
 }
 
 int orb_init(fvo_ctx* ctx) {
@@ -1197,6 +1307,18 @@ int orb_init(fvo_ctx* ctx) {
     ++v0;
   }
 
+  // Orientation inside k_brief<true> needs the disc (radius half) to consist of true pixels of
+  // the 45 x 45 patch that kernel stages around the keypoint:
+  //   half <= kAngR (15)          the disc fits the staged square (radius 22) and the 32 columns
+  //                               of a half-wave
+  //   edge_threshold >= half      a keypoint lies edge_threshold px inside its level, so no disc
+  //                               pixel is one the REFLECT_101 staging path mirrored in
+  // Any other configuration runs k_angle as a pass of its own before k_brief<false>.  Both hold
+  // for every configuration check_orb_config accepts today (patchSize 31, edgeThreshold >= 15):
+  // the separate pass is there for the day that check widens, and fvo_debug_buffer(10) switches a
+  // context to it so that tests and tools/bench_orb.py can run it.
+  g.angle_pass = half > kAngR || c.edge_threshold < half;
+
   // size-independent tables only: the geometry travels by value (OrbDev)
   FVO_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(c_umax), umax.data(), sizeof(int) * 20));
   FVO_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(c_pattern), FVO_ORB_PATTERN, sizeof(FVO_ORB_PATTERN)));
@@ -1213,13 +1335,15 @@ int orb_init(fvo_ctx* ctx) {
       (rc = fvo_alloc(ctx, &ctx->koff, B * (c.nlevels + 1))) ||
       (rc = fvo_alloc(ctx, &ctx->scratch, B * c.nlevels * ctx->scratch_per)))
     return rc;
-  // k_keep_compact: a lane per tile, at most 64 tiles across (width < 4096, check_orb_config)
-  if ((rc = fvo_alloc(ctx, &ctx->fast_rec, B * make_dev(g).tile0[g.nlevels] * kTRec))) return rc;
+  // one record per tile of the hot path's grid (the debug score map writes none)
+  if ((rc = fvo_alloc(ctx, &ctx->fast_rec, B * make_dev(g, c.edge_threshold).tile0[g.nlevels] * kTRec))) return rc;
   return 0;
 }
 
 namespace {
-OrbDev make_dev(const OrbGeom& g) {
+// org: the origin of the FAST tile grid -- edgeThreshold on the hot path, 0 for the whole-level
+// score map of the debug hook (k_fast_nms)
+OrbDev make_dev(const OrbGeom& g, int org) {
   OrbDev G{};
   G.nlevels = g.nlevels;
   G.total_rows = g.total_rows;
@@ -1232,9 +1356,11 @@ OrbDev make_dev(const OrbGeom& g) {
     G.cand_off[l] = g.cand_off[l];
     G.scale[l] = g.scale[l];
     G.nfeat[l] = g.nfeat[l];
-    G.ntx[l] = (g.w[l] + kTW - 1) / kTW;
+    // FAST tiles from (org, org) over the level less org px on every side
+    const int ew = g.w[l] - 2 * org, eh = g.h[l] - 2 * org;
+    G.ntx[l] = ew > 0 && eh > 0 ? (ew + kTW - 1) / kTW : 0;
     G.tile0[l] = t;
-    t += G.ntx[l] * ((g.h[l] + kTH - 1) / kTH);
+    t += G.ntx[l] ? G.ntx[l] * ((eh + kTH - 1) / kTH) : 0;
     G.bntx[l] = (g.w[l] + kBW - 1) / kBW;
     G.btile0[l] = bt;
     bt += G.bntx[l] * ((g.h[l] + kBH - 1) / kBH);
@@ -1257,7 +1383,7 @@ int orb_run(fvo_ctx* ctx, const uint8_t* images, int batch, int64_t image_stride
   const int W = c.width, H = c.height;
   const int64_t total = g.total_px;
   const int thr = std::min(std::max(c.fast_threshold, 0), 255);
-  const OrbDev G = make_dev(g);
+  const OrbDev G = make_dev(g, c.edge_threshold);
   const int ntiles = G.tile0[L];
   const bool vec = ((uintptr_t)images & 15) == 0 && (image_stride & 15) == 0 && (pitch & 15) == 0 && (W & 15) == 0 &&
                    (total & 15) == 0;
@@ -1276,8 +1402,9 @@ int orb_run(fvo_ctx* ctx, const uint8_t* images, int batch, int64_t image_stride
     FVO_TIMED(ctx, KN_ORB_RESIZE, s, hipLaunchKernelGGL(k_resize, dim3((g.w[l] + 256 * kResCols - 1) / (256 * kResCols), (g.h[l] + kResRows - 1) / kResRows, batch), dim3(256), 0, s, G, ctx->pyr, total, l,
                        ctx->rt.xofs + ctx->rt.xoff[l], ctx->rt.xc1 + ctx->rt.xoff[l], ctx->rt.yofs + ctx->rt.yoff[l],
                        ctx->rt.yc1 + ctx->rt.yoff[l]));
-  FVO_TIMED(ctx, KN_ORB_FAST, s, hipLaunchKernelGGL(k_fast_nms<false>, dim3(ntiles, batch), dim3(kFT), 0, s, G, ctx->pyr,
-                     nullptr, ctx->fast_rec, total, thr, c.edge_threshold, ntiles));
+  if (ntiles > 0)  // no level has an interior: k_select finds no rows to compact
+    FVO_TIMED(ctx, KN_ORB_FAST, s, hipLaunchKernelGGL(k_fast_nms<false>, dim3(ntiles, batch), dim3(kFT), 0, s, G, ctx->pyr,
+                       nullptr, ctx->fast_rec, total, thr, c.edge_threshold, c.edge_threshold, ntiles));
   FVO_TIMED(ctx, KN_ORB_SELECT1, s, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_select<ElemFast, kSelCap1, true>), dim3(batch, L),
                      dim3(kSelThreads), 0, s, G, ctx->fast_rec, ntiles, c.edge_threshold, ctx->cand, ctx->ncand,
                      ctx->nsel1, ctx->scratch, ctx->scratch_per, g.cand_total, L, 2));
@@ -1287,9 +1414,15 @@ int orb_run(fvo_ctx* ctx, const uint8_t* images, int batch, int64_t image_stride
                      dim3(kSelThreads), 0, s, G, nullptr, ntiles, c.edge_threshold, ctx->hel, ctx->nsel1,
                      ctx->nsel2, ctx->scratch, ctx->scratch_per, g.cand_total, L, 1));
   FVO_TIMED(ctx, KN_ORB_OFFSETS, s, hipLaunchKernelGGL(k_offsets, dim3((batch + 63) / 64), dim3(64), 0, s, ctx->nsel2, ctx->koff, counts, batch, L, cap));
-  FVO_TIMED(ctx, KN_ORB_ANGLE, s, hipLaunchKernelGGL(k_angle, dim3(16, L, batch), dim3(256), 0, s, G, ctx->pyr, ctx->hel, ctx->nsel2, ctx->koff, kp,
-                     total, g.cand_total, L, cap, c.patch_size));
-  FVO_TIMED(ctx, KN_ORB_BRIEF, s, hipLaunchKernelGGL(k_brief, dim3(64, batch), dim3(256), 0, s, G, ctx->pyr, kp, counts, desc, total, cap));
+  if (g.angle_pass) {
+    FVO_TIMED(ctx, KN_ORB_ANGLE, s, hipLaunchKernelGGL(k_angle, dim3(16, L, batch), dim3(256), 0, s, G, ctx->pyr, ctx->hel, ctx->nsel2, ctx->koff, kp,
+                       total, g.cand_total, L, cap, c.patch_size));
+    FVO_TIMED(ctx, KN_ORB_BRIEF, s, hipLaunchKernelGGL(k_brief<false>, dim3(64, batch), dim3(256), 0, s, G, ctx->pyr, ctx->hel, ctx->koff, kp, counts,
+                       desc, total, g.cand_total, L, cap, c.patch_size));
+  } else {
+    FVO_TIMED(ctx, KN_ORB_BRIEF, s, hipLaunchKernelGGL(k_brief<true>, dim3(64, batch), dim3(256), 0, s, G, ctx->pyr, ctx->hel, ctx->koff, kp, counts,
+                       desc, total, g.cand_total, L, cap, c.patch_size));
+  }
   ctx->orb_last_batch = batch;
   FVO_LAUNCH_CHECK(ctx);
   return 0;
@@ -1305,7 +1438,7 @@ int orb_blur_debug(fvo_ctx* ctx) {
     if (rc) return rc;
   }
   if (ctx->orb_last_batch > 0) {
-    const OrbDev G = make_dev(g);
+    const OrbDev G = make_dev(g, 0);  // the blur tiles do not depend on the FAST origin
     hipLaunchKernelGGL(k_blur, dim3(G.btile0[g.nlevels], ctx->orb_last_batch), dim3(256), 0, 0, G, ctx->pyr, ctx->blur,
                        g.total_px);
     FVO_LAUNCH_CHECK(ctx);
@@ -1324,11 +1457,13 @@ int orb_score_debug(fvo_ctx* ctx) {
     if (rc) return rc;
   }
   if (ctx->orb_last_batch > 0) {
-    const OrbDev G = make_dev(g);
+    // the score of every pixel of every level: a tile grid of its own, from (0, 0) over the
+    // whole levels, whatever grid the hot path lays
+    const OrbDev G = make_dev(g, 0);
     const int ntiles = G.tile0[g.nlevels];
     hipLaunchKernelGGL(k_fast_nms<true>, dim3(ntiles, ctx->orb_last_batch), dim3(kFT), 0, 0, G, ctx->pyr, ctx->score,
                        nullptr, g.total_px, std::min(std::max(ctx->cfg.fast_threshold, 0), 255),
-                       ctx->cfg.edge_threshold, ntiles);  // the threshold orb_run uses
+                       ctx->cfg.edge_threshold, 0, ntiles);  // the threshold orb_run uses
     FVO_LAUNCH_CHECK(ctx);
   }
   FVO_HIP(ctx, hipDeviceSynchronize());

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """ORB alone on the GPU (tooling): the bench step's ORB call -- 64 left + 64 right synthetic
 960x600 images, nfeatures 1000 -- with per-kernel times (HIP events) and the whole-call time.
-Prints one JSON line; FVO_LIB selects a variant library."""
+Prints one JSON line; FVO_LIB selects a variant library.  --angle-pass switches the context to
+the orientation as a pass of its own (k_angle, then the plain k_brief; fvo_debug_buffer 10)
+instead of inside k_brief."""
+import ctypes
 import json
 import os
 import sys
@@ -20,6 +23,9 @@ def main():
     L, R = seq.frames(range(B))
     imgs = torch.cat([L, R]).contiguous()
     ctx = _lib.Context(W, H, max_batch=2 * B, nfeatures=1000, stages=_lib.STAGE_ORB)
+    if "--angle-pass" in sys.argv[1:]:
+        p, nb = ctypes.c_void_p(), ctypes.c_int64()
+        assert ctx.L.fvo_debug_buffer(ctx.h, 10, ctypes.byref(p), ctypes.byref(nb)) == 0
     out = None
     for _ in range(2):
         out = ctx.orb(imgs)
