@@ -82,26 +82,22 @@ __global__ void k_copy_level0_v(const uint4* __restrict__ img, int64_t stride16,
   }
 }
 
-// INTER_LINEAR_EXACT level l from level l-1; a thread covers kResCols consecutive columns x
-// kResRows rows (the column tables are read once per thread).  The border cases are folded
-// into the weights (a clamped source index with weights 256 / 0 gives exactly the border
-// formulas: s << 8 for a column, (h + 128) >> 8 = (256 h + 32768) >> 16 for a row), so every
-// load is unconditional and the rows' loads are all in flight at once.  Interior threads read
-// the source bytes of their 4 columns as one 8-byte window per source row (three aligned
-// dwords, v_alignbyte) instead of 16 byte loads; a window never reaches past level l-1's
-// successor in the same image, so the aligned over-read stays inside the pyramid buffer.
-constexpr int kResRows = 4, kResCols = 4;
-__global__ void k_resize(const OrbDev G, uint8_t* __restrict__ pyr, int64_t total, int l, const int32_t* __restrict__ xofs,
-                         const int32_t* __restrict__ xc1, const int32_t* __restrict__ yofs,
-                         const int32_t* __restrict__ yc1) {
-  const XcdBlock xb = xcd_block();  // blocks sharing source rows on one XCD
-  const int x0 = (xb.x * blockDim.x + threadIdx.x) * kResCols;
-  const int b = xb.z;
-  const int w = G.w[l], h = G.h[l];
+// INTER_LINEAR_EXACT level l from level l-1.  The border cases are folded into the weights (a
+// clamped source index with weights 256 / 0 gives exactly the border formulas: s << 8 for a
+// column, (h + 128) >> 8 = (256 h + 32768) >> 16 for a row), so no load is conditional.
+//
+// resize_direct: the body for tiles whose source rectangle does not fit k_resize's LDS budget
+// (large scaleFactor).  The thread makes kResCols columns from x0 of `rows` rows from y0 straight
+// from global memory, row by row.  Interior threads read the source bytes of their 4 columns as
+// one 8-byte window per source row (three aligned dwords, v_alignbyte) instead of 16 byte loads;
+// a window never reaches past level l-1's successor in the same image, so the aligned over-read
+// stays inside the pyramid buffer.
+constexpr int kResCols = 4;
+__device__ __forceinline__ void resize_direct(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int w, int h,
+                                              int sw, int sh, int x0, int y0, int rows, const int32_t* __restrict__ xofs,
+                                              const int32_t* __restrict__ xc1, const int32_t* __restrict__ yofs,
+                                              const int32_t* __restrict__ yc1) {
   if (x0 >= w) return;
-  const int sw = G.w[l - 1], sh = G.h[l - 1];
-  const uint8_t* src = pyr + b * total + G.off[l - 1];
-  uint8_t* dst = pyr + b * total + G.off[l];
   int oxa[kResCols], oxb[kResCols];
   uint32_t cx0[kResCols], cx1[kResCols];
 #pragma unroll
@@ -122,10 +118,9 @@ __global__ void k_resize(const OrbDev G, uint8_t* __restrict__ pyr, int64_t tota
     const uint32_t w0 = q[0], w1 = q[1], w2 = q[2];
     return ((uint64_t)__builtin_amdgcn_alignbyte(w2, w1, sft) << 32) | __builtin_amdgcn_alignbyte(w1, w0, sft);
   };
-  uint32_t v[kResRows][kResCols];
-#pragma unroll
-  for (int k = 0; k < kResRows; ++k) {
-    const int y = min(xb.y * kResRows + k, h - 1);
+#pragma unroll 1
+  for (int y = y0; y < min(y0 + rows, h); ++y) {
+    uint32_t v[kResCols];
     const int oy = yofs[y];
     const int ra = oy >= 0 ? oy : (oy == -1 ? 0 : sh - 1), rb = oy >= 0 ? oy + 1 : ra;
     const uint32_t cy1 = oy >= 0 ? (uint32_t)yc1[y] : 0u, cy0 = 256u - cy1;
@@ -138,22 +133,175 @@ __global__ void k_resize(const OrbDev G, uint8_t* __restrict__ pyr, int64_t tota
         const int da = 8 * (oxa[i] - oxa[0]), db = 8 * (oxb[i] - oxa[0]);
         const uint32_t ha = cx0[i] * (uint32_t)((wa >> da) & 255u) + cx1[i] * (uint32_t)((wa >> db) & 255u);
         const uint32_t hb = cx0[i] * (uint32_t)((wb >> da) & 255u) + cx1[i] * (uint32_t)((wb >> db) & 255u);
-        v[k][i] = (ha * cy0 + hb * cy1 + 32768u) >> 16;
+        v[i] = (ha * cy0 + hb * cy1 + 32768u) >> 16;
       }
     } else {
 #pragma unroll
       for (int i = 0; i < kResCols; ++i) {
         const uint32_t ha = cx0[i] * sa[oxa[i]] + cx1[i] * sa[oxb[i]], hb = cx0[i] * sb[oxa[i]] + cx1[i] * sb[oxb[i]];
-        v[k][i] = (ha * cy0 + hb * cy1 + 32768u) >> 16;
+        v[i] = (ha * cy0 + hb * cy1 + 32768u) >> 16;
       }
     }
-  }
-#pragma unroll
-  for (int k = 0; k < kResRows; ++k) {
-    const int y = xb.y * kResRows + k;
 #pragma unroll
     for (int i = 0; i < kResCols; ++i)
-      if (y < h && x0 + i < w) dst[(int64_t)y * w + x0 + i] = (uint8_t)(v[k][i] > 255u ? 255u : v[k][i]);
+      if (x0 + i < w) dst[(int64_t)y * w + x0 + i] = (uint8_t)(v[i] > 255u ? 255u : v[i]);
+  }
+}
+
+// One block per kRzTW x kRzTH output tile of level l (one launch per level; no block waits for
+// another).  The tile's source rectangle of level l-1 -- columns c0..c1 and rows r0..r1, from
+// xofs / yofs at the tile's corners (the tables are monotone, clamped entries included) -- is
+// staged in LDS with aligned 16-byte loads; row rr lands at rr * pitch16 + (its global
+// address & 15), so each row keeps its own byte phase (level widths are odd).  A thread owns 4
+// output columns (cg) and the kRzSR rows of one strip, and walks the strip's rows top down:
+//   horizontal  per source row, h[i] = cx0[i] * s[oxa[i]] + cx1[i] * s[oxb[i]] (<= 65280, u16)
+//               from one 8-byte LDS window (three aligned dwords, v_alignbyte, then a v_perm
+//               per column).  Consecutive output rows share a source row (rb of one = ra of
+//               the next, 4 times in 5 at scale 1.2); the shared row's h is kept in registers.
+//   vertical    (ha * cy0 + hb * cy1 + 32768) >> 16, clamped to 255 (acc >= 2^24 <=> v > 255).
+//               All integer, so any evaluation order gives the same bytes.
+//   store       the tile row starts at byte phase a = (off[l] + y * w + tx0) & 3 of its image
+//               (the images are 256-aligned), so lane cg takes the upper a bytes of lane
+//               cg - 1 and stores the aligned dword that covers tile columns 4 cg - a ..
+//               4 cg - a + 3; a dword that straddles the tile's sides is stored byte by byte
+//               (the bytes inside the tile only), and the last lane also stores its own upper
+//               a bytes.
+// Memory safety, per image [img, img + total), img = pyr + b * total:
+//   loads   16-byte blocks from the one holding the rectangle's first byte of a row to the one
+//           holding its last.  Both bytes lie in level l-1, i.e. in [img, img + off[l]); img is
+//           256-aligned and total = off[nlevels] rounded up to 256 >= off[l] rounded up to 16,
+//           so the blocks lie in [img, img + total).
+//   stores  only bytes of columns [tx0, tx0 + tw) of rows < h of level l.
+// If the rectangle exceeds the LDS budget, or a thread's 4 columns span more than 8 source
+// bytes, the whole block (a block-uniform branch) makes its tile with resize_direct.
+constexpr int kRzTW = 128, kRzTH = 64, kRzSR = 8;  // tile; rows of a strip (32 column groups x 8 strips)
+constexpr int kRzLds = 1024;                       // LDS budget of the source rectangle, 16-byte units
+static_assert(kRzTW == 32 * kResCols && kRzTH == 8 * kRzSR, "resize tile shape");
+__global__ __launch_bounds__(256) void k_resize(const OrbDev G, uint8_t* __restrict__ pyr, int64_t total, int l,
+                                                const int32_t* __restrict__ xofs, const int32_t* __restrict__ xc1,
+                                                const int32_t* __restrict__ yofs, const int32_t* __restrict__ yc1) {
+  __shared__ uint4 s_src[kRzLds + 1];  // + 1: a window's third dword may lie past the last staged block
+  const int tid = threadIdx.x, cg = tid & 31, strip = tid >> 5;
+  const int tx0 = blockIdx.x * kRzTW, ty0 = blockIdx.y * kRzTH, b = blockIdx.z;
+  const int w = G.w[l], h = G.h[l], sw = G.w[l - 1], sh = G.h[l - 1];
+  uint8_t* img = pyr + b * total;
+  const int tw = min(kRzTW, w - tx0), th = min(kRzTH, h - ty0);
+  auto first = [](int o, int n) { return o >= 0 ? o : (o == -1 ? 0 : n - 1); };
+  auto last = [](int o, int n) { return o >= 0 ? o + 1 : (o == -1 ? 0 : n - 1); };
+  const int c0 = first(xofs[tx0], sw), c1 = last(xofs[tx0 + tw - 1], sw);
+  const int r0 = first(yofs[ty0], sh), r1 = last(yofs[ty0 + th - 1], sh);
+  const int ncols = c1 - c0 + 1, nrows = r1 - r0 + 1;
+  const int pitch16 = (ncols + 15 + 15) >> 4;  // any 16-byte phase
+  // the thread's columns: window offset in the rectangle, byte selectors, packed weights
+  const int x0 = tx0 + cg * kResCols;
+  int wofs = 0, span = 0;
+  uint32_t sel[kResCols], cxw[kResCols];
+#pragma unroll
+  for (int i = 0; i < kResCols; ++i) {
+    const int x = min(x0 + i, w - 1);
+    const int ox = xofs[x], oa = first(ox, sw), ob = last(ox, sw);
+    const uint32_t c = ox >= 0 ? (uint32_t)xc1[x] : 0u;
+    if (i == 0) wofs = oa;
+    span = ob - wofs;
+    sel[i] = 0x0c000c00u | (uint32_t)(oa - wofs) | ((uint32_t)(ob - wofs) << 16);  // bytes: a, 0, b, 0
+    cxw[i] = (256u - c) | (c << 16);
+  }
+  if (!__syncthreads_and(span <= 7) || pitch16 * nrows > kRzLds) {
+    resize_direct(img + G.off[l - 1], img + G.off[l], w, h, sw, sh, x0, ty0 + strip * kRzSR, kRzSR, xofs, xc1, yofs, yc1);
+    return;
+  }
+  wofs -= c0;
+
+  // the strip's rows, read before the staging loads so that they share one round trip:
+  // ra (row of the rectangle, < kRzLds / 2) | (rb - ra) << 10 | cy1 << 16
+  uint32_t rinfo[kRzSR];
+#pragma unroll
+  for (int k = 0; k < kRzSR; ++k) {
+    const int yc = min(ty0 + strip * kRzSR + k, h - 1), oy = yofs[yc];
+    rinfo[k] = (uint32_t)(first(oy, sh) - r0) | ((uint32_t)(last(oy, sh) - first(oy, sh)) << 10) |
+               ((oy >= 0 ? (uint32_t)yc1[yc] : 0u) << 16);
+  }
+  // staging: block i = rr * pitch16 + j of the LDS rectangle is block j of row rr; the budget
+  // makes it at most kRzLds / 256 blocks per thread, all loaded before the first LDS write
+  const int64_t g0 = G.off[l - 1] + (int64_t)r0 * sw + c0;  // the rectangle's first byte, from img
+  uint4 stage[kRzLds / 256];
+#pragma unroll
+  for (int k = 0; k < kRzLds / 256; ++k) {
+    const int i = tid + 256 * k, rr = i / pitch16, j = i - rr * pitch16;
+    const int64_t ga = g0 + (int64_t)rr * sw;
+    const int nblk = (((int)ga & 15) + ncols + 15) >> 4;  // <= pitch16
+    const bool ok = rr < nrows && j < nblk;  // otherwise: the rectangle's first block again, unused
+    stage[k] = reinterpret_cast<const uint4*>(img + ((ok ? ga : g0) & ~(int64_t)15))[ok ? j : 0];
+  }
+#pragma unroll
+  for (int k = 0; k < kRzLds / 256; ++k)
+    if (tid + 256 * k < nrows * pitch16) s_src[tid + 256 * k] = stage[k];
+  __syncthreads();
+
+  typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+  const uint32_t* lds = reinterpret_cast<const uint32_t*>(s_src);
+  const int g0lo = (int)g0 & 15;
+  // h of the thread's columns at source row r0 + rr
+  auto hrow = [&](int rr, uint32_t (&hv)[kResCols]) {
+    const uint32_t p = (uint32_t)(rr * pitch16 * 16 + ((g0lo + rr * sw) & 15) + wofs);
+    const uint32_t* q = lds + (p >> 2);
+    const uint32_t w0 = q[0], w1 = q[1], w2 = q[2], sft = p & 3;
+    const uint32_t lo = __builtin_amdgcn_alignbyte(w1, w0, sft), hi = __builtin_amdgcn_alignbyte(w2, w1, sft);
+#pragma unroll
+    for (int i = 0; i < kResCols; ++i)
+      hv[i] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(hi, lo, sel[i])),
+                                     __builtin_bit_cast(us2, cxw[i]), 0u, false);
+  };
+  uint8_t* dst = img + G.off[l] + tx0;
+  uint32_t hp[kResCols] = {};
+  int prb = -1;
+#pragma unroll
+  for (int k = 0; k < kRzSR; ++k) {
+    const int y = ty0 + strip * kRzSR + k;
+    const int ra = (int)(rinfo[k] & 1023u), rb = ra + (int)((rinfo[k] >> 10) & 1u);
+    const uint32_t cy = rinfo[k] >> 16, cyw = (256u - cy) | (cy << 16);
+    uint32_t ha[kResCols], hb[kResCols], acc[kResCols];
+    if (ra == prb) {
+#pragma unroll
+      for (int i = 0; i < kResCols; ++i) ha[i] = hp[i];
+    } else {
+      hrow(ra, ha);
+    }
+    if (rb == ra) {
+#pragma unroll
+      for (int i = 0; i < kResCols; ++i) hb[i] = ha[i];
+    } else {
+      hrow(rb, hb);
+    }
+    prb = rb;
+#pragma unroll
+    for (int i = 0; i < kResCols; ++i) {
+      hp[i] = hb[i];
+      acc[i] = min(__builtin_amdgcn_udot2(__builtin_bit_cast(us2, ha[i] | (hb[i] << 16)), __builtin_bit_cast(us2, cyw),
+                                          32768u, false), 0xFFFFFFu);
+    }
+    // byte 2 of each acc is the pixel
+    const uint32_t own = __builtin_amdgcn_perm(__builtin_amdgcn_perm(acc[3], acc[2], 0x0c0c0602u),
+                                               __builtin_amdgcn_perm(acc[1], acc[0], 0x0c0c0602u), 0x05040100u);
+    const uint32_t prev = __shfl_up(own, 1, 32);
+    const int a = (int)((G.off[l] + (int64_t)y * w + tx0) & 3);
+    const uint32_t dw = (uint32_t)((((uint64_t)own << 32) | prev) >> (8 * (4 - a)));
+    if (y < h) {
+      uint8_t* row = dst + (int64_t)y * w;
+      const int cd = cg * kResCols - a;  // tile column of dw's byte 0
+      if (cd >= 0 && cd + 3 < tw) {
+        *reinterpret_cast<uint32_t*>(row + cd) = dw;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (cd + j >= 0 && cd + j < tw) row[cd + j] = (uint8_t)(dw >> (8 * j));
+      }
+      if (cg == 31) {  // the columns past the last lane's dword: its own upper a bytes
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if (j < a && cd + 4 + j < tw) row[cd + 4 + j] = (uint8_t)(own >> (8 * (4 - a + j)));
+      }
+    }
   }
 }
 
@@ -1399,7 +1547,7 @@ int orb_run(fvo_ctx* ctx, const uint8_t* images, int batch, int64_t image_stride
                                                       images, image_stride, pitch, ctx->pyr, total, W, H));
   }
   for (int l = 1; l < L; ++l)
-    FVO_TIMED(ctx, KN_ORB_RESIZE, s, hipLaunchKernelGGL(k_resize, dim3((g.w[l] + 256 * kResCols - 1) / (256 * kResCols), (g.h[l] + kResRows - 1) / kResRows, batch), dim3(256), 0, s, G, ctx->pyr, total, l,
+    FVO_TIMED(ctx, KN_ORB_RESIZE, s, hipLaunchKernelGGL(k_resize, dim3((g.w[l] + kRzTW - 1) / kRzTW, (g.h[l] + kRzTH - 1) / kRzTH, batch), dim3(256), 0, s, G, ctx->pyr, total, l,
                        ctx->rt.xofs + ctx->rt.xoff[l], ctx->rt.xc1 + ctx->rt.xoff[l], ctx->rt.yofs + ctx->rt.yoff[l],
                        ctx->rt.yc1 + ctx->rt.yoff[l]));
   if (ntiles > 0)  // no level has an interior: k_select finds no rows to compact

@@ -1146,9 +1146,75 @@ __global__ __launch_bounds__(64, D <= 96 ? 4 : 2) void k_sg_rows(const uint16_t*
 // ------------------------------------------------------------------ median 3x3
 // fail (may be null): pairs whose L-path hand-off timed out come out invalid everywhere;
 // status (may be null): per pair FVO_SGBM_OK / FVO_SGBM_HANDOFF_TIMEOUT, for the caller
-__global__ void k_sg_median(const int16_t* __restrict__ raw, int16_t* __restrict__ out, int W, int H,
-                            const uint32_t* __restrict__ fail, int16_t invalid, int32_t* __restrict__ status) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
+//
+// Vector body (every row of raw and out 16-byte aligned: W % 8 == 0 and both bases aligned, so
+// there is no row tail either): a thread makes 8 consecutive pixels of kMedRows rows.  It loads
+// the kMedRows + 2 source rows once (16 bytes plus the left and right neighbour each), forms the
+// x-1 / x / x+1 operands as packed i16 pairs and runs Paeth's 19 exchanges with v_pk_min/max_i16.
+// The network's first 9 exchanges sort each source row's (x-1, x, x+1) triple on its own, so they
+// are done once per loaded row and shared by the three output rows that read it.  Any other
+// shape takes the per-pixel body; sg_median_grid lays the grid by the same predicate.
+typedef short sg_s2 __attribute__((ext_vector_type(2)));
+constexpr int kMedRows = 4;
+__host__ __device__ inline bool sg_median_vec(const void* raw, const void* out, int W) {
+  return W % 8 == 0 && (((uintptr_t)raw | (uintptr_t)out) & 15) == 0;
+}
+inline dim3 sg_median_grid(const void* raw, const void* out, int W, int H, int nb) {
+  if (sg_median_vec(raw, out, W)) return dim3(((W / 8) * ((H + kMedRows - 1) / kMedRows) + 255) / 256, 1, nb);
+  return dim3((W + 255) / 256, H, nb);
+}
+
+#define SG_PK(a, b) { const sg_s2 t_ = __builtin_elementwise_min(a, b); b = __builtin_elementwise_max(a, b); a = t_; }
+__device__ __forceinline__ void sg_median_rows8(const int16_t* __restrict__ s, int16_t* __restrict__ o, int W, int H,
+                                                int x0, int y0, bool bad, int16_t invalid) {
+  // t[k][j][0..2]: sorted (x-1, x, x+1) of source row y0 - 1 + k (clamped), pixel pair j
+  sg_s2 t[kMedRows + 2][4][3];
+#pragma unroll
+  for (int k = 0; k < kMedRows + 2; ++k) {
+    const int16_t* row = s + (int64_t)min(max(y0 - 1 + k, 0), H - 1) * W;
+    const uint4 c4 = *reinterpret_cast<const uint4*>(row + x0);
+    const uint32_t c[4] = {c4.x, c4.y, c4.z, c4.w};
+    const uint32_t l = (uint16_t)row[max(x0 - 1, 0)], r = (uint16_t)row[min(x0 + 8, W - 1)];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t lo = j ? (c[j - 1] >> 16) | (c[j] << 16) : l | (c[0] << 16);
+      const uint32_t hi = j < 3 ? (c[j] >> 16) | (c[j + 1] << 16) : (c[3] >> 16) | (r << 16);
+      sg_s2 a = __builtin_bit_cast(sg_s2, lo), m = __builtin_bit_cast(sg_s2, c[j]), z = __builtin_bit_cast(sg_s2, hi);
+      SG_PK(m, z) SG_PK(a, m) SG_PK(m, z)
+      t[k][j][0] = a, t[k][j][1] = m, t[k][j][2] = z;
+    }
+  }
+  const uint32_t inv2 = (uint16_t)invalid * 0x10001u;
+#pragma unroll
+  for (int k = 0; k < kMedRows; ++k) {
+    uint32_t res[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      sg_s2 v0 = t[k][j][0], v1 = t[k][j][1], v2 = t[k][j][2], v3 = t[k + 1][j][0], v4 = t[k + 1][j][1],
+            v5 = t[k + 1][j][2], v6 = t[k + 2][j][0], v7 = t[k + 2][j][1], v8 = t[k + 2][j][2];
+      SG_PK(v0, v3) SG_PK(v5, v8) SG_PK(v4, v7) SG_PK(v3, v6) SG_PK(v1, v4) SG_PK(v2, v5) SG_PK(v4, v7) SG_PK(v4, v2)
+      SG_PK(v6, v4) SG_PK(v4, v2)
+      res[j] = bad ? inv2 : __builtin_bit_cast(uint32_t, v4);
+    }
+    if (y0 + k < H) *reinterpret_cast<uint4*>(o + (int64_t)(y0 + k) * W + x0) = make_uint4(res[0], res[1], res[2], res[3]);
+  }
+}
+#undef SG_PK
+
+__global__ __launch_bounds__(256) void k_sg_median(const int16_t* __restrict__ raw, int16_t* __restrict__ out, int W, int H,
+                                                   const uint32_t* __restrict__ fail, int16_t invalid,
+                                                   int32_t* __restrict__ status) {
+  const int b = blockIdx.z;
+  if (sg_median_vec(raw, out, W)) {
+    const int W8 = W >> 3, i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool bad = fail && fail[b];
+    if (status && i == 0) status[b] = bad ? FVO_SGBM_HANDOFF_TIMEOUT : FVO_SGBM_OK;
+    const int yg = i / W8;
+    if (yg * kMedRows >= H) return;
+    sg_median_rows8(raw + (int64_t)b * W * H, out + (int64_t)b * W * H, W, H, (i - yg * W8) * 8, yg * kMedRows, bad, invalid);
+    return;
+  }
+  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (status && x == 0 && y == 0) status[b] = (fail && fail[b]) ? FVO_SGBM_HANDOFF_TIMEOUT : FVO_SGBM_OK;
   if (x >= W) return;
   const int16_t* s = raw + (int64_t)b * W * H;
@@ -1211,7 +1277,7 @@ void launch_sgbm(fvo_ctx* ctx, const SgParams& p, const uint8_t* L, const uint8_
     FVO_TIMED(ctx, KN_SG_VERT, s, hipLaunchKernelGGL(kern, gcv, dim3(gg * cb), 0, s, L, R, stride, pitch, p, V, M, lk));
     FVO_TIMED(ctx, KN_SG_ROWS, s, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sg_rows<D, kSwBoth>), dim3(sg_nblk(p), nb), dim3(64), 0, s,
                                                      V, M, p, ctx->sg_ckpt, nck, ctx->sg_raw));
-    FVO_TIMED(ctx, KN_SG_MEDIAN, s, hipLaunchKernelGGL(k_sg_median, dim3((p.W + 255) / 256, p.H, nb), dim3(256), 0, s,
+    FVO_TIMED(ctx, KN_SG_MEDIAN, s, hipLaunchKernelGGL(k_sg_median, sg_median_grid(ctx->sg_raw, disp, p.W, p.H, nb), dim3(256), 0, s,
                                                        ctx->sg_raw, disp, p.W, p.H, nullptr, invalid, status));
     return;
   }
@@ -1224,7 +1290,7 @@ void launch_sgbm(fvo_ctx* ctx, const SgParams& p, const uint8_t* L, const uint8_
                                                    p, V, M, lk));
   FVO_TIMED(ctx, KN_SG_ROWS, s, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sg_rows<D, kSwRight>), dim3(sg_nblk(p), nb), dim3(64), 0, s,
                                                    V, M, p, ctx->sg_ckpt, nck, ctx->sg_raw));
-  FVO_TIMED(ctx, KN_SG_MEDIAN, s, hipLaunchKernelGGL(k_sg_median, dim3((p.W + 255) / 256, p.H, nb), dim3(256), 0, s,
+  FVO_TIMED(ctx, KN_SG_MEDIAN, s, hipLaunchKernelGGL(k_sg_median, sg_median_grid(ctx->sg_raw, disp, p.W, p.H, nb), dim3(256), 0, s,
                                                      ctx->sg_raw, disp, p.W, p.H, ctx->sg_ctl + 4, invalid, status));
 }
 
