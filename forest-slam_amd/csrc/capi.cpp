@@ -448,6 +448,24 @@ int fvo_undistort_gray(fvo_ctx* c, const uint8_t* bgr, int32_t batch, int64_t sr
   const int W = c->cfg.width, H = c->cfg.height;
   if (src_pitch < 3 * W || src_stride < (int64_t)src_pitch * H || dst_pitch < W || dst_stride < (int64_t)dst_pitch * H)
     return fvo_fail(c, "bad pitch/stride");
+  // fvo_rectify_map's calibration rule for every stripe of cv2.undistort: the kernel inverts K with
+  // cy moved to the stripe's first row and divides by _w = (i*ir[7] + ir[8]) + col*ir[6], i the
+  // row inside the stripe.  _w is affine in (i, col): the stripe's four corners bound it.
+  if (!host_all_finite(K, 9) || !host_all_finite(dist, 5))
+    return fvo_fail(c, "undistort_gray: K and dist must be finite");
+  const int stripe0 = ingest_stripe_rows(W, H);
+  for (int y0 = 0; y0 < H; y0 += stripe0) {
+    double A[9], ir[9];
+    std::memcpy(A, K, sizeof(A));
+    A[5] = K[5] - y0;
+    if (!host_inv3(A, ir)) return fvo_fail(c, "undistort_gray: K is singular (a stripe's camera matrix has det == 0)");
+    const int rows = H - y0 < stripe0 ? H - y0 : stripe0;
+    for (int k = 0; k < 4; ++k) {
+      const int i = (k >> 1) ? rows - 1 : 0, col = (k & 1) ? W - 1 : 0;
+      if (!host_ray_w_ok((i * ir[7] + ir[8]) + col * ir[6]))
+        return fvo_fail(c, "undistort_gray: _w <= 0 at a stripe corner (the view reaches the camera's horizon)");
+    }
+  }
   return ingest_run(c, bgr, batch, src_stride, src_pitch, K, dist, gray, dst_stride, dst_pitch, (hipStream_t)stream);
 }
 

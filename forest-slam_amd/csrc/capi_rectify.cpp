@@ -11,34 +11,12 @@
 
 namespace {
 
-// OpenCV invert() 3x3 closed form (as csrc/ingest.hip, oracle/ingest_ref.cpp); false: det == 0
-bool inv3(const double* S, double* t) {
-  double d = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6]);
-  if (d == 0.) return false;
-  d = 1. / d;
-  t[0] = (S[4] * S[8] - S[5] * S[7]) * d;
-  t[1] = (S[2] * S[7] - S[1] * S[8]) * d;
-  t[2] = (S[1] * S[5] - S[2] * S[4]) * d;
-  t[3] = (S[5] * S[6] - S[3] * S[8]) * d;
-  t[4] = (S[0] * S[8] - S[2] * S[6]) * d;
-  t[5] = (S[2] * S[3] - S[0] * S[5]) * d;
-  t[6] = (S[3] * S[7] - S[4] * S[6]) * d;
-  t[7] = (S[1] * S[6] - S[0] * S[7]) * d;
-  t[8] = (S[0] * S[4] - S[1] * S[3]) * d;
-  return true;
-}
-
-bool all_finite(const double* v, int n) {
-  for (int i = 0; i < n; ++i)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-
 // The calibration checks shared by fvo_rectify_map and fvo_rectify_gray; fills L on success.
 int make_lens(fvo_ctx* c, const double* K, const double* dist, int32_t n_dist, const double* R, const double* newK,
               RectifyLens* L) {
   if (n_dist != 4 && n_dist != 5 && n_dist != 8) return fvo_fail(c, "rectify: n_dist must be 4, 5 or 8");
-  if (!all_finite(K, 9) || !all_finite(dist, n_dist) || (R && !all_finite(R, 9)) || (newK && !all_finite(newK, 9)))
+  if (!host_all_finite(K, 9) || !host_all_finite(dist, n_dist) || (R && !host_all_finite(R, 9)) ||
+      (newK && !host_all_finite(newK, 9)))
     return fvo_fail(c, "rectify: K, dist, R and newK must be finite");
   const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   const double* Rm = R ? R : I;
@@ -46,13 +24,13 @@ int make_lens(fvo_ctx* c, const double* K, const double* dist, int32_t n_dist, c
   double A[9];  // newK * R, each entry (a0 b0 + a1 b1) + a2 b2
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) A[3 * i + j] = (Nk[3 * i] * Rm[j] + Nk[3 * i + 1] * Rm[3 + j]) + Nk[3 * i + 2] * Rm[6 + j];
-  if (!inv3(A, L->ir)) return fvo_fail(c, "rectify: newK*R is singular");
+  if (!host_inv3(A, L->ir)) return fvo_fail(c, "rectify: newK*R is singular");
   // _w is affine in (row, col): the four corners bound it over the image
   const int W = c->cfg.width, H = c->cfg.height;
   for (int k = 0; k < 4; ++k) {
     const int row = (k >> 1) ? H - 1 : 0, col = (k & 1) ? W - 1 : 0;
     const double w = (row * L->ir[7] + L->ir[8]) + col * L->ir[6];
-    if (!(w > 0.0) || !std::isfinite(1. / w))
+    if (!host_ray_w_ok(w))
       return fvo_fail(c, "rectify: _w <= 0 at an image corner (the view reaches the camera's horizon)");
   }
   L->fx = K[0]; L->fy = K[4]; L->u0 = K[2]; L->v0 = K[5];

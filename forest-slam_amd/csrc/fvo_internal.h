@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -197,6 +198,39 @@ int pnp_run(fvo_ctx* ctx, const float* P3, const float* p2, const int32_t* npts,
             const double* dist, float reproj, double conf, int iters, double* rvec, double* tvec, double* T,
             int32_t* status, uint8_t* inliers, hipStream_t s);
 
+// Host arithmetic of the calibration checks (capi.cpp, capi_rectify.cpp).  inv3: OpenCV invert() 3x3
+// closed form, operation for operation as the device copies (csrc/ingest.hip, oracle/ingest_ref.cpp),
+// so det == 0 here is det == 0 there; false: det == 0.
+inline bool host_inv3(const double* S, double* t) {
+  double d = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6]);
+  if (d == 0.) return false;
+  d = 1. / d;
+  t[0] = (S[4] * S[8] - S[5] * S[7]) * d;
+  t[1] = (S[2] * S[7] - S[1] * S[8]) * d;
+  t[2] = (S[1] * S[5] - S[2] * S[4]) * d;
+  t[3] = (S[5] * S[6] - S[3] * S[8]) * d;
+  t[4] = (S[0] * S[8] - S[2] * S[6]) * d;
+  t[5] = (S[2] * S[3] - S[0] * S[5]) * d;
+  t[6] = (S[3] * S[7] - S[4] * S[6]) * d;
+  t[7] = (S[1] * S[6] - S[0] * S[7]) * d;
+  t[8] = (S[0] * S[4] - S[1] * S[3]) * d;
+  return true;
+}
+inline bool host_all_finite(const double* v, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+// is the ray denominator w > 0 with a finite reciprocal (the kernels divide by it)
+inline bool host_ray_w_ok(double w) { return w > 0.0 && std::isfinite(1. / w); }
+
+// cv2.undistort's stripe height (oracle/ingest_ref.cpp): the rows that share one camera matrix, K with
+// cy moved to the stripe's first row.  ingest_run launches with it, fvo_undistort_gray checks every
+// stripe's matrix.
+inline int ingest_stripe_rows(int W, int H) {
+  const int s = 4096 / (W > 1 ? W : 1);
+  return s < 1 ? 1 : (s > H ? H : s);
+}
 int ingest_run(fvo_ctx* ctx, const uint8_t* bgr, int batch, int64_t sstride, int spitch, const double* K,
                const double* dist, uint8_t* gray, int64_t dstride, int dpitch, hipStream_t s);
 int motion_blur_run(fvo_ctx* ctx, const uint8_t* img, int batch, int64_t sstride, int spitch, int ksize,

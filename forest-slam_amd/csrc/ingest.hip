@@ -117,8 +117,7 @@ int ingest_run(fvo_ctx* ctx, const uint8_t* bgr, int batch, int64_t sstride, int
   Lens L;
   for (int i = 0; i < 9; ++i) L.K[i] = K[i];
   L.k1 = dist[0]; L.k2 = dist[1]; L.p1 = dist[2]; L.p2 = dist[3]; L.k3 = dist[4];
-  int stripe0 = 4096 / (W > 1 ? W : 1);
-  stripe0 = stripe0 < 1 ? 1 : (stripe0 > H ? H : stripe0);
+  const int stripe0 = ingest_stripe_rows(W, H);
   constexpr int PIX = 4;
   dim3 grid((W + 64 * PIX - 1) / (64 * PIX), (H + 3) / 4, batch);
   const bool pinhole = K[1] == 0.0 && K[3] == 0.0 && K[6] == 0.0 && K[7] == 0.0 && K[8] == 1.0;

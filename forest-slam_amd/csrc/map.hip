@@ -25,6 +25,12 @@
 
 namespace {
 
+// the points of set j that are appended: n_points[j] clamped to [0, cap] (as fvo_gather_matches clamps
+// its counts; a negative count is an empty set, not a step backwards in the map)
+__device__ __forceinline__ int64_t set_count(const int32_t* __restrict__ npts, int j, int64_t cap) {
+  return max((int64_t)0, min((int64_t)npts[j], cap));
+}
+
 __global__ __launch_bounds__(256) void k_map_xform(const float* __restrict__ pts, int stride, int64_t cap,
                                                    const int32_t* __restrict__ npts, int batch,
                                                    const double* __restrict__ T, const int32_t* __restrict__ count,
@@ -32,13 +38,13 @@ __global__ __launch_bounds__(256) void k_map_xform(const float* __restrict__ pts
                                                    float* __restrict__ out32) {
   const int b = blockIdx.y;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t n = min((int64_t)npts[b], cap);
+  const int64_t n = set_count(npts, b, cap);
   if ((int64_t)blockIdx.x * 256 >= n) return;  // uniform: no point of set b in this block
   // the set's offset in the map: one wave sums the counts of the sets before it
   __shared__ int64_t s_base;
   if (threadIdx.x < 64) {
     int64_t part = 0;
-    for (int j = threadIdx.x; j < b; j += 64) part += min((int64_t)npts[j], cap);
+    for (int j = threadIdx.x; j < b; j += 64) part += set_count(npts, j, cap);
     part = wave_sum(part);
     if (threadIdx.x == 0) s_base = count[0] + part;
   }
@@ -64,7 +70,7 @@ __global__ __launch_bounds__(256) void k_map_xform(const float* __restrict__ pts
 __global__ void k_map_count(const int32_t* __restrict__ npts, int batch, int64_t cap, int32_t* __restrict__ count) {
   if (threadIdx.x != 0) return;
   int64_t t = count[0];
-  for (int j = 0; j < batch; ++j) t += min((int64_t)npts[j], cap);
+  for (int j = 0; j < batch; ++j) t += set_count(npts, j, cap);
   count[0] = (int32_t)min(t, (int64_t)INT32_MAX);
 }
 

@@ -300,7 +300,15 @@ int fvo_recover_pose(fvo_ctx* ctx, const double* E, const int32_t* e_status, con
  * followed by cv2.cvtColor(., COLOR_BGR2GRAY).  Image size = the context's width x height.
  * bgr:  [batch] images, image b at bgr + b*src_stride, rows src_pitch (>= 3*width) bytes apart.
  * K:    host double[9] row-major; dist: host double[5] (k1 k2 p1 p2 k3).
- * gray: [batch] u8 images at gray + b*dst_stride, rows dst_pitch bytes apart. */
+ * gray: [batch] u8 images at gray + b*dst_stride, rows dst_pitch bytes apart.
+ * Refused, as fvo_rectify_map refuses them, but per stripe of cv2.undistort (stripe =
+ * min(max(1, 4096 / width), height) rows; the stripe starting at row y0 uses K with K[5] - y0):
+ * a non-finite entry of K or dist; a K for which some stripe's matrix has det == 0 by the 3x3
+ * closed form; a K for which some stripe's ray denominator _w = ir[6]*col + ir[7]*i + ir[8] (ir
+ * the inverse of the stripe's matrix, i the row inside the stripe) is not > 0 with a finite
+ * reciprocal at one of the stripe's four corners.  OpenCV defines no output for these (the map
+ * would be NaN); finite coefficients of any size are accepted (map entries saturate as cvRound
+ * does). */
 int fvo_undistort_gray(fvo_ctx* ctx, const uint8_t* bgr, int32_t batch, int64_t src_stride, int32_t src_pitch,
                        const double* K, const double* dist, uint8_t* gray, int64_t dst_stride, int32_t dst_pitch,
                        fvo_stream stream);
@@ -358,7 +366,10 @@ int fvo_rectify_lds_budget(fvo_ctx* ctx, int32_t bytes);
  * other angles return an error).  filter2D arithmetic: direct float path for k*k < 130, exact
  * S/k (the DFT path's value) otherwise — see csrc/ingest.hip.
  * centers: [batch][centers_cap] int32 flat pixel indices y*W+x (random.sample(range(H*W), n)),
- *          n_centers [batch] device counts (<= centers_cap); centers_cap 0 = no blur (mask empty).
+ *          n_centers [batch] device counts; centers_cap 0 (centers may then be NULL) = no blur
+ *          (mask empty).  Image b uses its first min(max(n_centers[b], 0), centers_cap) entries: a
+ *          count above centers_cap is clamped to it, a negative count is an empty list.  An entry
+ *          outside [0, H*W) is not a pixel and is ignored (it blurs nothing); duplicates are fine.
  * mask:    [batch][H][W] u8 device buffer (4-byte aligned), written (0/1).
  * img/out: [batch] u8 images (b*stride, rows pitch bytes apart); out must not alias img. */
 int fvo_motion_blur(fvo_ctx* ctx, const uint8_t* img, int32_t batch, int64_t src_stride, int32_t src_pitch,
@@ -366,13 +377,16 @@ int fvo_motion_blur(fvo_ctx* ctx, const uint8_t* img, int32_t batch, int64_t src
                     uint8_t* mask, uint8_t* out, int64_t dst_stride, int32_t dst_pitch, fvo_stream stream);
 
 /* Map accumulation (any stage; no workspace).  For each of `batch` point sets b (float32 xyz,
- * point p of set b at points + (b*cap + p)*point_stride, n_points[b] device counts <= cap) and
+ * point p of set b at points + (b*cap + p)*point_stride, point_stride >= 3 floats (e.g. 4 for the
+ * [cap][4] stereo records; floats past xyz are not read), n_points[b] device counts) and
  * its 4x4 row-major fp64 transform T[b] (device, [batch][16]):
  *   x' = ((T[0] x + T[1] y) + T[2] z) + T[3]   (likewise rows 1, 2; fp64, no contraction)
  * appended to the map in set order starting at *map_count (device), which is then advanced by
- * the total.  map_xyz64 (fp64, [map_cap][3]) and/or map_xyz32 (the PointCloud2 FLOAT32 x/y/z
- * record, [map_cap][3]) may be NULL (not both); points past map_cap are dropped while
- * *map_count still counts them (caller checks for overflow). */
+ * the total (saturating at INT32_MAX).  Every count is clamped to [0, cap] as fvo_gather_matches
+ * clamps its counts: n_points[b] < 0 counts as 0 (an empty set; it moves neither the later sets
+ * nor *map_count backwards), n_points[b] > cap as cap.  map_xyz64 (fp64, [map_cap][3]) and/or
+ * map_xyz32 (the PointCloud2 FLOAT32 x/y/z record, [map_cap][3]) may be NULL (not both); points
+ * past map_cap are dropped while *map_count still counts them (caller checks for overflow). */
 int fvo_map_transform(fvo_ctx* ctx, const float* points, int32_t point_stride, const int32_t* n_points, int32_t batch,
                       int64_t cap, const double* T, int32_t* map_count, int64_t map_cap, double* map_xyz64,
                       float* map_xyz32, fvo_stream stream);

@@ -8,6 +8,7 @@
 
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <string>
 
 #include "host_stubs.h"
@@ -160,6 +161,59 @@ static void config_checks() {
   b = stage_config(FVO_STAGE_ALL); b.ba_window = 2; b.block_size = 5; create_refused(b, "SGBM: only blockSize=7 is supported");
   b.nlevels = 13; create_refused(b, "nlevels out of range");
   b = stage_config(FVO_STAGE_POSE | FVO_STAGE_MONO); create_reached(b, "mono_init");
+}
+
+// ---- the calibration refusals of fvo_undistort_gray by their messages, and every lens case of
+// tests/ingest_cases.py accepted, on a context of W x H
+static void lens_checks(fvo_ctx* c, int W, int H) {
+  static uint8_t img[8];  // the stub launcher never dereferences it
+  const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+  auto call = [&](const double* K, const double* d) {
+    g_last_launch.clear();
+    return fvo_undistort_gray(c, img, 1, (int64_t)3 * W * H, 3 * W, K, d, img, (int64_t)W * H, W, nullptr);
+  };
+  const char* finite = "undistort_gray: K and dist must be finite";
+  const char* singular = "undistort_gray: K is singular (a stripe's camera matrix has det == 0)";
+  const char* horizon = "undistort_gray: _w <= 0 at a stripe corner (the view reaches the camera's horizon)";
+  const double Kc[9] = {70, 0, 48.3, 0, 69, 37.6, 0, 0, 1}, Kskew[9] = {70, 0.8, 48.3, 0, 69, 37.6, 0, 0, 1};
+  const double K8[9] = {140, 0, 96.6, 0, 138, 75.2, 0, 0, 2};
+  const double Kpersp[9] = {70, 0.8, 48.3, 0.3, 69, 37.6, 2e-4, -3e-4, 1};
+  const double tang[5] = {-0.2, 0.05, 0.01, -0.02, 0.03}, pin[5] = {0.4, 0.1, 0.003, 0.002, 0.05};
+  const double dpersp[5] = {0.1, 0.05, 0.01, -0.02, 0.03}, sat[5] = {1e7, 0, 0, 0, 0};
+  reached(call(Kc, tang), "ingest_run");
+  reached(call(Kc, pin), "ingest_run");
+  reached(call(Kskew, tang), "ingest_run");
+  reached(call(K8, tang), "ingest_run");
+  reached(call(Kpersp, dpersp), "ingest_run");
+  reached(call(Kc, sat), "ingest_run");  // finite, and only large
+  double K[9], d[5];
+  std::memcpy(K, Kc, sizeof(K)); K[0] = 0; refused(c, call(K, tang), singular);
+  std::memcpy(K, Kc, sizeof(K)); K[8] = 0; refused(c, call(K, tang), singular);
+  // _w changes sign across the width: with K[6] = 2 it runs from -2.7 at column 0 to +2.1 at column
+  // 63 (4.9 at column 99, 72 at column 959).  K[6] = -0.02 does not do that: _w stays inside
+  // [0.986, 1.26] up to 960x600, a lens the rule accepts.
+  std::memcpy(K, Kpersp, sizeof(K)); K[6] = 2.0; refused(c, call(K, dpersp), horizon);
+  std::memcpy(K, Kpersp, sizeof(K)); K[6] = -0.02; reached(call(K, dpersp), "ingest_run");
+  std::memcpy(K, Kc, sizeof(K)); K[8] = -1; refused(c, call(K, tang), horizon);           // _w < 0 everywhere
+  for (int i = 0; i < 5; ++i) {
+    std::memcpy(d, tang, sizeof(d)); d[i] = nan; refused(c, call(Kc, d), finite);
+    std::memcpy(d, tang, sizeof(d)); d[i] = -inf; refused(c, call(Kc, d), finite);
+  }
+  for (int i = 0; i < 9; ++i) {
+    std::memcpy(K, Kc, sizeof(K)); K[i] = inf; refused(c, call(K, tang), finite);
+    std::memcpy(K, Kc, sizeof(K)); K[i] = nan; refused(c, call(K, tang), finite);
+  }
+  // the rule holds per stripe: with K[7] = -1 the determinant 70 * (69 + (K[5] - y0)) vanishes in the
+  // stripe that starts at row y0 = K[5] + 69 and nowhere else
+  const int stripe = 4096 / W < 1 ? 1 : (4096 / W > H ? H : 4096 / W);
+  if (stripe < H) {
+    const double Kstripe[9] = {70, 0, 48.3, 0, 69, (double)stripe - 69, 0, -1, 1};
+    refused(c, call(Kstripe, tang), singular);
+  }
+  if (stripe < H && 2 * stripe >= H) {  // two stripes: the determinant is > 0 in both and zero at row stripe + 1
+    const double Kbetween[9] = {70, 0, 48.3, 0, 69, (double)stripe - 68, 0, -1, 1};
+    reached(call(Kbetween, tang), "ingest_run");
+  }
 }
 
 int main() {
@@ -342,8 +396,10 @@ int main() {
                    "recover_run");
 
   // ---- ingest / blur
-  reset(); rejected(c, fvo_undistort_gray(c, u8, 1, 3 * W * H, 3 * W - 1, f64, f64, u8, W * H, W, nullptr));
-  reset(); reached(fvo_undistort_gray(c, u8, 1, 3 * W * H, 3 * W, f64, f64, u8, W * H, W, nullptr), "ingest_run");
+  const double Kc[9] = {70, 0, 48.3, 0, 69, 37.6, 0, 0, 1}, tang[5] = {-0.2, 0.05, 0.01, -0.02, 0.03};
+  reset(); rejected(c, fvo_undistort_gray(c, u8, 1, 3 * W * H, 3 * W - 1, Kc, tang, u8, W * H, W, nullptr));
+  reset(); reached(fvo_undistort_gray(c, u8, 1, 3 * W * H, 3 * W, Kc, tang, u8, W * H, W, nullptr), "ingest_run");
+  lens_checks(c, W, H);
   reset(); rejected(c, fvo_motion_blur(c, u8, 1, W * H, W, 10, 0.5, i32, i32, 16, u8, u8 + 8, W * H, W, nullptr));
   reset(); rejected(c, fvo_motion_blur(c, u8, 1, W * H, W, 32, 0.0, i32, i32, 16, u8, u8 + 8, W * H, W, nullptr));
   reset(); rejected(c, fvo_motion_blur(c, u8, 1, W * H, W, 10, 0.0, i32, i32, 16, u8, u8, W * H, W, nullptr));
@@ -450,6 +506,16 @@ int main() {
   reset(); refused(c, fvo_debug_buffer(c, 9, &ptr, &bytes), "no SGBM workspace");
   fvo_destroy(c);
   CHECK(g_live_allocs == 0);
+
+  // the lens cases at their own size: two stripes of 40 rows
+  cfg.width = 100;
+  cfg.height = 76;
+  CHECK(fvo_create(0, &cfg, &c) == 0);
+  lens_checks(c, 100, 76);
+  fvo_destroy(c);
+  CHECK(g_live_allocs == 0);
+  cfg.width = 960;
+  cfg.height = 600;
 
   // a mono context whose capacity passes the essential-matrix LDS bound
   cfg.stages = FVO_STAGE_MONO;

@@ -97,11 +97,13 @@ def test_golden_blur_reproduces(oracle_mod):
         assert np.array_equal(out, g[f"out{k}"]) and np.array_equal(mask, g[f"mask{k}"])
 
 
-@pytest.mark.parametrize("k", [3, 10, 11, 12, 15, 20])
-def test_blur_oracle_matches_exact_sum(oracle_mod, k):
+BLUR_KS = [1, 2, 3, 10, 11, 12, 15, 20, 30, 31]
+
+
+def check_blur_oracle_against_exact_sum(oracle_mod, k, H, W):
     rng = np.random.default_rng(k)
-    img = rng.integers(0, 256, (48, 70), dtype=np.uint8)
-    centers = rng.choice(48 * 70, 40, replace=False).astype(np.int32)
+    img = rng.integers(0, 256, (H, W), dtype=np.uint8)
+    centers = rng.choice(H * W, 40, replace=False).astype(np.int32)
     out, mask = oracle_mod.motion_blur(img, k, centers)
     exact, tie, mask_np = _blur_numpy(img, k, centers)
     assert np.array_equal(mask, mask_np)
@@ -112,6 +114,13 @@ def test_blur_oracle_matches_exact_sum(oracle_mod, k):
         q = np.floor(exact - 0.5)
         want = np.where(q % 2 == 0, q, q + 1)
         assert np.array_equal(out[(mask == 1) & tie], want[(mask == 1) & tie].astype(np.uint8))
+    if k == 1:  # a one-tap kernel: the image itself
+        assert np.array_equal(out, img)
+
+
+@pytest.mark.parametrize("k", BLUR_KS)
+def test_blur_oracle_matches_exact_sum(oracle_mod, k):
+    check_blur_oracle_against_exact_sum(oracle_mod, k, 48, 70)
 
 
 def test_blur_zero_percent_is_identity(oracle_mod):

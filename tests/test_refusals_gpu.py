@@ -97,6 +97,36 @@ def test_voxel_workspace_one_byte_short():
         ctx.h, p(pts), n, 0.5, p(ws), wb - 1, p(out), p(cnt), None, None)))
 
 
+def _lens(base, **entries):
+    """A lens of tests/ingest_cases.py with entries of K (k0..k8) or dist (d0..d4) replaced."""
+    import ingest_cases as ic
+    K, d = ic.lens(base)
+    K, d = K.reshape(9).copy(), d.copy()
+    for name, v in entries.items():
+        (K if name[0] == "k" else d)[int(name[1:])] = v
+    return K, d
+
+
+# What cv2.undistort defines no output for (the map would be NaN): refused as fvo_rectify_map refuses
+# it.  `_w` changes sign across the 64 columns with K[6] = 2 (-2.7 at column 0, +2.1 at column 63).
+@pytest.mark.parametrize("base, entries, message", [
+    ("tang", dict(k0=0.0), "undistort_gray: K is singular (a stripe's camera matrix has det == 0)"),
+    ("tang", dict(k8=0.0), "undistort_gray: K is singular (a stripe's camera matrix has det == 0)"),
+    ("persp", dict(k6=2.0), "undistort_gray: _w <= 0 at a stripe corner (the view reaches the camera's horizon)"),
+    ("tang", dict(d3=float("nan")), "undistort_gray: K and dist must be finite"),
+    ("tang", dict(k2=float("inf")), "undistort_gray: K and dist must be finite"),
+], ids=["K0=0", "K8=0", "w-changes-sign", "nan-in-dist", "inf-in-K"])
+def test_undistort_gray_refuses_lens(base, entries, message):
+    K, d = _lens(base, **entries)
+    _refused(message, _ctx("BF").undistort_gray, _z((1, 64, 64, 3), torch.uint8), K, d)
+
+
+def test_undistort_gray_accepts_the_lens_cases():
+    import ingest_cases as ic
+    for name in ic.LENSES:
+        _ctx("BF").undistort_gray(_z((1, 64, 64, 3), torch.uint8), *ic.lens(name))
+
+
 # width 80 for the 16-bit case: at 64 columns every accepted numDisparities leaves no column
 # ("image narrower than numDisparities" comes first)
 @pytest.mark.parametrize("stage, size, cfg, message", [
