@@ -36,6 +36,12 @@ class FvoRegion(ctypes.Structure):
     _fields_ = [("dst", ctypes.c_void_p), ("src", ctypes.c_void_p), ("bytes", ctypes.c_int64)]
 
 
+class FvoSparseStereoParams(ctypes.Structure):
+    """fvo_sparse_stereo_params of include/fvo.h."""
+    _fields_ = [(n, ctypes.c_float) for n in ("min_disparity", "max_disparity", "row_tol")] + [
+        (n, ctypes.c_int32) for n in ("max_hamming", "max_octave_diff", "half_window", "half_slide", "unique")]
+
+
 FVO_MAX_REGIONS = 32
 ABI_VERSION = 7  # FVO_ABI_VERSION of include/fvo.h
 STAGE_ORB, STAGE_BF, STAGE_SGBM, STAGE_POSE, STAGE_BA, STAGE_MONO = 1, 2, 4, 8, 16, 32
@@ -92,6 +98,12 @@ SIGNATURES = {
     "fvo_dense_map_append": (ctypes.c_int, [_P, _P, _I, _I, _I, _L, _I, _P, ctypes.c_double, _I, _I, ctypes.c_float,
                                             ctypes.c_float, _P, _P, _P, _L, _P, _P, _P, _P, _L, _P]),
     "fvo_reproject_to_3d": (ctypes.c_int, [_P, _P, _I, _I, _I, _I, _L, _I, _P, _I, _P, _P, _P]),
+    "fvo_sparse_stereo_params_default": (None, [ctypes.POINTER(FvoSparseStereoParams)]),
+    "fvo_sparse_stereo_workspace_bytes": (ctypes.c_int64, [_I, _I]),
+    "fvo_sparse_stereo": (ctypes.c_int, [_P, _P, _P, _I, _L, _I, _P, _P, _P, _P, _P, _P, _I,
+                                         ctypes.POINTER(FvoSparseStereoParams), _P, _I, _P, ctypes.c_double, _P, _L, _P,
+                                         _P, _P]),
+    "fvo_backproject_stereo": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "fvo_motion_blur": (ctypes.c_int, [_P, _P, _I, _L, _I, _I, ctypes.c_double, _P, _P, _I, _P, _P, _L, _I, _P]),
     "fvo_test_retain_best": (ctypes.c_int, [_P, _P, _I, _I, _P, _P, _P]),
     "fvo_debug_buffer": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
@@ -744,6 +756,85 @@ class Context:
                                                pitch, Qh, int(bool(handle_missing)), _ptr(key), _ptr(out),
                                                _stream(self.device)))
         return out
+
+    def sparse_stereo_params(self, **kw) -> FvoSparseStereoParams:
+        """fvo_sparse_stereo_params_default with the given fields replaced."""
+        p = FvoSparseStereoParams()
+        self.L.fvo_sparse_stereo_params_default(ctypes.byref(p))
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise TypeError(f"unknown fvo_sparse_stereo_params field {k}")
+            setattr(p, k, v)
+        return p
+
+    def sparse_stereo_workspace_bytes(self, batch: int, cap: int) -> int:
+        """fvo_sparse_stereo_workspace_bytes: scratch bytes of sparse_stereo for [batch, cap]."""
+        wb = int(self.L.fvo_sparse_stereo_workspace_bytes(int(batch), int(cap)))
+        if wb < 0:
+            raise ValueError(f"sparse_stereo: unsupported size batch={batch} cap={cap}")
+        return wb
+
+    def level_scales(self) -> np.ndarray:
+        """The context's ORB level scales as sparse_stereo takes them: float32(scale_factor ** o)."""
+        return np.array([float(self.cfg.scale_factor) ** o for o in range(int(self.cfg.nlevels))], np.float32)
+
+    def sparse_stereo(self, left, right, kpL, nL, descL, kpR, nR, descR, K, baseline, params=None, level_scale=None,
+                      workspace=None, out=None, info=None):
+        """Per-keypoint stereo records from left-right ORB matches (fvo_sparse_stereo; the rule:
+        tests/sparse_stereo_ref.py).  left/right u8 [B,H,W] (or [H,W]) of the context's size, rows
+        and images may be spaced; kp* f32 [B,cap,8], n* i32 [B], desc* u8 [B,cap,32].  params: a
+        sparse_stereo_params() struct or a dict of its fields; level_scale: float32 per octave
+        (default level_scales()).  workspace: uint8 device tensor of >= sparse_stereo_workspace_bytes(B,
+        cap) bytes, allocated here only when none is passed.  info: int32 [B,cap,4] to receive
+        (right index, hamming, k*, status), or None.  Returns stereo f32 [B,cap,4] = (X, Y, Z, d),
+        zeros where no point was found; rows >= nL are not written."""
+        l, B, _, istride, pitch = self._u8_images(left, "sparse_stereo left", 1)
+        r, Br, _, rstride, rpitch = self._u8_images(right, "sparse_stereo right", 1)
+        if (Br, rstride, rpitch) != (B, istride, pitch):
+            raise ValueError("sparse_stereo: left and right must have the same batch, stride and pitch")
+        cap = kpL.shape[1]
+        for t, shape, dt in ((kpL, (B, cap, KP_STRIDE), torch.float32), (kpR, (B, cap, KP_STRIDE), torch.float32),
+                             (descL, (B, cap, DESC_BYTES), torch.uint8), (descR, (B, cap, DESC_BYTES), torch.uint8)):
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise TypeError(f"sparse_stereo: expected a contiguous {dt} {list(shape)} tensor")
+        if out is None:
+            out = torch.empty((B, cap, 4), dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (B, cap, 4) or not out.is_contiguous():
+            raise TypeError(f"sparse_stereo: out must be a contiguous float32 [{B},{cap},4] tensor")
+        if info is not None and (info.dtype != torch.int32 or tuple(info.shape) != (B, cap, 4) or
+                                 not info.is_contiguous()):
+            raise TypeError(f"sparse_stereo: info must be a contiguous int32 [{B},{cap},4] tensor")
+        if B == 0:
+            return out
+        if params is None or isinstance(params, dict):
+            params = self.sparse_stereo_params(**(params or {}))
+        ls = np.ascontiguousarray(self.level_scales() if level_scale is None else level_scale, np.float32)
+        wb = self.sparse_stereo_workspace_bytes(B, cap)
+        if workspace is None:
+            workspace = torch.empty((wb,), dtype=torch.uint8, device=self.device)
+        elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < wb:
+            raise ValueError(f"sparse_stereo: workspace must be a contiguous uint8 tensor of >= {wb} bytes")
+        Kh = (ctypes.c_double * 9)(*[float(v) for v in np.asarray(K, np.float64).reshape(-1)])
+        self._check(self.L.fvo_sparse_stereo(self.h, _ptr(l), _ptr(r), B, istride, pitch, _ptr(kpL), _ptr(nL),
+                                             _ptr(descL), _ptr(kpR), _ptr(nR), _ptr(descR), cap, ctypes.byref(params),
+                                             ls.ctypes.data_as(ctypes.c_void_p), len(ls), Kh, float(baseline),
+                                             _ptr(workspace), workspace.numel(), _ptr(out), _ptr(info),
+                                             _stream(self.device)))
+        return out
+
+    def backproject_stereo(self, stereo, kp1, matches, nmatch, out=None):
+        """backproject() with the depth taken from the stereo record of the match's query keypoint
+        (fvo_backproject_stereo): the records with Z != 0, compacted in match order."""
+        B, cap = matches.shape[0], matches.shape[1]
+        if out is None:
+            P3 = torch.empty((B, cap, 3), dtype=torch.float32, device=self.device)
+            p2 = torch.empty((B, cap, 2), dtype=torch.float32, device=self.device)
+            n = torch.empty((B,), dtype=torch.int32, device=self.device)
+        else:
+            P3, p2, n = out
+        self._check(self.L.fvo_backproject_stereo(self.h, _ptr(stereo), None, _ptr(kp1), _ptr(matches), _ptr(nmatch),
+                                                  B, cap, _ptr(P3), _ptr(p2), _ptr(n), _stream(self.device)))
+        return P3, p2, n
 
     def gather_matches(self, kp0, kp1, matches, nmatch, out=None):
         """mkpts0/mkpts1 of a BF match list (fvo_gather_matches): (p0 f32[B,cap,2], p1, n i32[B])."""

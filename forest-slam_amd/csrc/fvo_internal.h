@@ -286,6 +286,22 @@ int remap_run(fvo_ctx* ctx, const uint8_t* src, int batch, int64_t sstride, int 
               const int16_t* map1, const uint16_t* map2, uint8_t* dst, int64_t dstride, int dpitch, hipStream_t s);
 int rectify_gray_run(fvo_ctx* ctx, const uint8_t* src, int batch, int64_t sstride, int spitch, int channels,
                      const RectifyLens& L, uint8_t* gray, int64_t dstride, int dpitch, hipStream_t s);
+// Sparse stereo (sparse_stereo.hip).  capi_stereo.cpp validates the parameters and hands the
+// launcher the level scales by value.  ws: two u32 key planes [batch][cap] (left rows, right columns).
+constexpr int kSparseMaxLevels = 32;
+constexpr int kSparseMaxHalfWindow = 7, kSparseMaxHalfSlide = 8;  // sparse_stereo.hip sizes its LDS by them
+struct SparseLevels {
+  float scale[kSparseMaxLevels];
+  int n;
+};
+int sparse_stereo_run(fvo_ctx* ctx, const uint8_t* left, const uint8_t* right, int batch, int64_t image_stride,
+                      int pitch, const float* kpL, const int32_t* nL, const uint8_t* descL, const float* kpR,
+                      const int32_t* nR, const uint8_t* descR, int cap, const fvo_sparse_stereo_params& p,
+                      const SparseLevels& levels, const double* K, double baseline, void* ws, float* stereo,
+                      int32_t* info, hipStream_t s);
+int backproject_stereo_run(fvo_ctx* ctx, const float* stereo, const float* kp1, const int32_t* matches,
+                           const int32_t* nmatch, int batch, int cap, float* P3, float* p2, int32_t* npts,
+                           hipStream_t s);
 int mono_init(fvo_ctx* ctx);
 int gather_run(fvo_ctx* ctx, const float* kp0, const float* kp1, const int32_t* matches, const int32_t* nmatch,
                int batch, int cap, float* p0, float* p1, int32_t* npts, hipStream_t s);

@@ -72,8 +72,12 @@ def _upload(msgs, dev):
 def run_stereo_bag(path: str, batch: int = 32, nfeatures: int = 500, frame_interval: int = 1, ba_window: int = 0,
                    device="cuda:0", K_left=K0, dist_left=DIST_L, K_right=K1, dist_right=DIST_R, baseline=BASELINE,
                    point_map=None, speckle_window: int = 0, speckle_range: int = 0, match_ratio: float = 0.0,
-                   dense_map=None, dense_step: int = 4, dense_z_max: float = 1000.0, rectify=None):
+                   dense_map=None, dense_step: int = 4, dense_z_max: float = 1000.0, rectify=None,
+                   depth: str = "sgbm", sparse_params: dict | None = None):
     """stereo_slam.py's ORB branch over a bag -> (TUM rows f64[n,8], relative T, statuses).
+    depth: "sgbm" = the reference's depth from a disparity map of every pair; "sparse" = per-keypoint
+    depth from left-right ORB matches (vo.StereoFrontEnd(depth="sparse"), sparse_params its
+    parameters): no disparity map is computed, so it cannot feed dense_map.
     match_ratio: > 0 keeps only the cross-checked matches that pass Lowe's ratio test at that
     ratio (0 = the reference's matcher).
     speckle_window / speckle_range: StereoSGBM_create's speckleWindowSize / speckleRange (0 = off,
@@ -89,6 +93,8 @@ def run_stereo_bag(path: str, batch: int = 32, nfeatures: int = 500, frame_inter
     camera; bgr8 and mono8 images), the front end runs with the rectified camera matrix, zero
     distortion and the rectified baseline (the `baseline` argument is not used), and the poses
     are those of the RECTIFIED left camera: x_rect = R1 x_left."""
+    if depth == "sparse" and dense_map is not None:
+        raise ValueError('run_stereo_bag: depth="sparse" computes no disparity map for dense_map')
     bag = rosbag.Bag(path)
     pairs = select_stereo_pairs(bag, frame_interval)
     if len(pairs) < 2:
@@ -106,7 +112,8 @@ def run_stereo_bag(path: str, batch: int = 32, nfeatures: int = 500, frame_inter
     fe = vo.StereoFrontEnd(W, H, K_left if rect is None else rect.K_rect, dist_left if rect is None else np.zeros(5),
                            baseline if rect is None else rect.baseline, batch=batch, nfeatures=nfeatures,
                            device=device, ba_window=ba_window, speckle_window=speckle_window,
-                           speckle_range=speckle_range, match_ratio=match_ratio)
+                           speckle_range=speckle_range, match_ratio=match_ratio, depth=depth,
+                           sparse_params=sparse_params)
     ctx, dev = fe.ctx, fe.dev
 
     def gray(lo, hi):

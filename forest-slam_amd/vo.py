@@ -8,6 +8,9 @@ fixed sequence of HIP launches (no host synchronisation inside):
   kept for work-equivalence with the reference)                (:234,242)
   SGBM of the B *previous* stereo pairs                         (:262 -> :108-117)
   back-projection of the matched previous-left keypoints        (:265-289)
+  (depth="sparse": instead of the two, the per-keypoint stereo records of the current pairs from
+  their left-right ORB matches, fvo_sparse_stereo, and the back-projection through the records
+  of the previous-left frames -- no disparity map and no SGBM workspace)
   PnP-RANSAC + Rodrigues -> relative T                          (:292-303)
   local BA over the last K frames of every new frame            (north_star; oracle/ba_ref.py)
 
@@ -55,7 +58,13 @@ class StereoFrontEnd:
     def __init__(self, width: int, height: int, K: np.ndarray, dist: np.ndarray, baseline: float, batch: int,
                  nfeatures: int = 500, match_right: bool = True, device=None, ba_window: int = 10,
                  ba_iters: int = 10, overlap_sgbm: bool = False, sgbm_last: bool = False, births_ahead: bool = False,
-                 speckle_window: int = 0, speckle_range: int = 0, match_ratio: float = 0.0, **params):
+                 speckle_window: int = 0, speckle_range: int = 0, match_ratio: float = 0.0, depth: str = "sgbm",
+                 sparse_params: dict | None = None, **params):
+        if depth not in ("sgbm", "sparse"):
+            raise ValueError('depth must be "sgbm" or "sparse"')
+        self.sparse = depth == "sparse"
+        if self.sparse and speckle_window:
+            raise ValueError('depth="sparse" computes no disparity map: speckle_window does not apply')
         self.B = batch
         self.match_ratio = _match_ratio(match_ratio)
         self.K = np.asarray(K, np.float64)
@@ -64,11 +73,12 @@ class StereoFrontEnd:
         self.match_right = match_right
         self.ba_window = int(ba_window)
         self.ba_iters = int(ba_iters)
-        stages = _lib.STAGE_ORB | _lib.STAGE_BF | _lib.STAGE_SGBM | _lib.STAGE_POSE
+        stages = _lib.STAGE_ORB | _lib.STAGE_BF | _lib.STAGE_POSE | (0 if self.sparse else _lib.STAGE_SGBM)
         if self.ba_window:
             stages |= _lib.STAGE_BA
             params.setdefault("ba_window", self.ba_window)
-        params.setdefault("sgbm_max_batch", batch)  # SGBM runs on the step's B pairs (ORB on 2B images)
+        if not self.sparse:
+            params.setdefault("sgbm_max_batch", batch)  # SGBM runs on the step's B pairs (ORB on 2B images)
         self.ctx = _lib.Context(width, height, max_batch=2 * batch, device=device, nfeatures=nfeatures,
                                 stages=stages, **params)
         self.dev = self.ctx.device
@@ -88,11 +98,22 @@ class StereoFrontEnd:
         self.q_kp_buf = two((B, cap, _lib.KP_STRIDE), torch.float32)
         self.matches_buf = two((2 * B, cap, 3), torch.int32)
         self.nmatch_buf = two((2 * B,), torch.int32)
-        self.prevL = e((B, height, width), torch.uint8)
-        self.prevR = e((B, height, width), torch.uint8)
-        self.disp_buf = two((B, height, width), torch.int16)
-        self.sg_status_buf = two((B,), torch.int32)
-        self.sgbm_can_fail = int(self.ctx.cfg.sgbm_mode) == _lib.SGBM_LPATH
+        if self.sparse:
+            # the sparse records (X, Y, Z, d per left keypoint) of the step's current pairs, of the
+            # last pair (kept across steps, written by prime()) and of the step's previous-left
+            # frames: the last pair's, then the current ones' [:n-1] -- q_kp's order.  The back
+            # stage and the BA read the latter, so it has two slots like q_kp.
+            self.sparse_params = self.ctx.sparse_stereo_params(**(sparse_params or {}))
+            self.level_scale = self.ctx.level_scales()
+            self.cur_stereo = torch.zeros((B, cap, 4), dtype=torch.float32, device=dev)
+            self.last_stereo = torch.zeros((cap, 4), dtype=torch.float32, device=dev)
+            self.q_stereo_buf = [torch.zeros((B, cap, 4), dtype=torch.float32, device=dev) for _ in range(2)]
+            self.sparse_ws = e((self.ctx.sparse_stereo_workspace_bytes(B, cap),), torch.uint8)
+        self.prevL = None if self.sparse else e((B, height, width), torch.uint8)
+        self.prevR = None if self.sparse else e((B, height, width), torch.uint8)
+        self.disp_buf = [None, None] if self.sparse else two((B, height, width), torch.int16)
+        self.sg_status_buf = [None, None] if self.sparse else two((B,), torch.int32)
+        self.sgbm_can_fail = not self.sparse and int(self.ctx.cfg.sgbm_mode) == _lib.SGBM_LPATH
         # StereoSGBM_create(speckleWindowSize=, speckleRange=): cv2.filterSpeckles on the step's
         # disparity maps right after SGBM (0 = off, the reference's setting: no launch).  Its
         # scratch is used on the front stage's stream only, so one allocation serves both slots.
@@ -102,7 +123,10 @@ class StereoFrontEnd:
                                        device=dev) if self.speckle_window > 0 else None)
         # the BA's per-keypoint stereo points of the step's previous-left frames, computed in the
         # front stage (they need only its disparities and keypoints) into a slot like disp
-        self.kstereo_buf = two((B, cap, 4), torch.float32) if self.ba_window else [None, None]
+        # (depth="sparse": they ARE the records of the previous-left frames, so kstereo and q_stereo
+        # name the same two slots and no fvo_keypoint_stereo is launched)
+        self.kstereo_buf = (self.q_stereo_buf if self.sparse else
+                            two((B, cap, 4), torch.float32) if self.ba_window else [None, None])
         self._select(0)
         self.P3 = e((B, cap, 3), torch.float32)
         self.p2 = e((B, cap, 2), torch.float32)
@@ -150,8 +174,8 @@ class StereoFrontEnd:
         self.s_births = torch.cuda.Stream(dev) if (self.ba_window and births_ahead) else None
         # prime() runs on the caller's stream: the first front stage after it waits for it
         self.primed = None
-        self.sg_lastL = e((height, width), torch.uint8)
-        self.sg_lastR = e((height, width), torch.uint8)
+        self.sg_lastL = None if self.sparse else e((height, width), torch.uint8)
+        self.sg_lastR = None if self.sparse else e((height, width), torch.uint8)
         self.main_done = [None, None]
         self.k = 0
         self.has_prev = False
@@ -160,8 +184,11 @@ class StereoFrontEnd:
         """Feed the first stereo pair of a sequence (no pose is produced for it)."""
         imgs = torch.stack([L0, R0]).to(self.dev)
         kp, desc, cnt = self.ctx.orb(imgs)
-        self.sg_lastL.copy_(imgs[0])
-        self.sg_lastR.copy_(imgs[1])
+        if self.sparse:
+            self._sparse_stereo(imgs, kp, desc, cnt, 1, self.last_stereo[None])
+        else:
+            self.sg_lastL.copy_(imgs[0])
+            self.sg_lastR.copy_(imgs[1])
         self.last_kp.copy_(kp[0])
         self.last_desc.copy_(desc[:2])
         self.last_cnt.copy_(cnt[:2])
@@ -212,9 +239,10 @@ class StereoFrontEnd:
             # dozen separate copies: (A) the SGBM pairs and the ORB images, (B) after ORB the
             # query sets (previous descriptors / counts / keypoints) and the last images,
             # (C) after BF the last frame's keypoints / descriptors / counts
-            ctx.copy_regions(self._sgbm_pairs(L, R, n) + [(self.imgs[:n], L), (self.imgs[n:2 * n], R)])
+            ctx.copy_regions(([] if self.sparse else self._sgbm_pairs(L, R, n)) +
+                             [(self.imgs[:n], L), (self.imgs[n:2 * n], R)])
             # SGBM first: ORB + BF first measured slower (r3 4242 vs 4284, r4 5051 vs 5227 frames/s)
-            if not self.sgbm_last:
+            if not self.sgbm_last and not self.sparse:
                 disp = self._sgbm(n)
             kp, desc, cnt = ctx.orb(self.imgs[:2 * n], out=(self.kp[:2 * n], self.desc[:2 * n], self.cnt[:2 * n]))
             # query (previous) sets: left frames then right frames; previous-left keypoints
@@ -222,17 +250,24 @@ class StereoFrontEnd:
                               (self.q_desc[1:n], desc[:n - 1]), (self.q_cnt[1:n], cnt[:n - 1]),
                               (self.q_desc[n], self.last_desc[1]), (self.q_cnt[n:n + 1], self.last_cnt[1:2]),
                               (self.q_desc[n + 1:2 * n], desc[n:2 * n - 1]), (self.q_cnt[n + 1:2 * n], cnt[n:2 * n - 1]),
-                              (self.q_kp[0], self.last_kp), (self.q_kp[1:n], kp[:n - 1]),
-                              (self.sg_lastL, L[n - 1]), (self.sg_lastR, R[n - 1])])
+                              (self.q_kp[0], self.last_kp), (self.q_kp[1:n], kp[:n - 1])] +
+                             ([] if self.sparse else [(self.sg_lastL, L[n - 1]), (self.sg_lastR, R[n - 1])]))
             nb = 2 * n if self.match_right else n
             m, nm = _match(ctx, self.match_ratio, self.q_desc[:nb], self.q_cnt[:nb], desc[:nb], cnt[:nb],
                            out=(self.matches[:nb], self.nmatch[:nb]))
             ctx.copy_regions([(self.last_kp, kp[n - 1]), (self.last_desc[0], desc[n - 1]),
                               (self.last_desc[1], desc[2 * n - 1]), (self.last_cnt[0:1], cnt[n - 1:n]),
                               (self.last_cnt[1:2], cnt[2 * n - 1:2 * n])])
-            if self.sgbm_last:
+            if self.sparse:
+                # the current pairs' records; the previous-left frames' are the last pair's, then
+                # these [:n-1]; the last pair's is replaced only after it was read
+                self._sparse_stereo(self.imgs, kp, desc, cnt, n, self.cur_stereo[:n])
+                ctx.copy_regions([(self.q_stereo[0], self.last_stereo), (self.q_stereo[1:n], self.cur_stereo[:n - 1])])
+                ctx.copy_regions([(self.last_stereo, self.cur_stereo[n - 1])])
+                disp = None
+            elif self.sgbm_last:
                 disp = self._sgbm(n)
-            if self.ba_window:  # (a negative count -- ORB overflow -- reads as no keypoints)
+            if self.ba_window and not self.sparse:  # (a negative count -- ORB overflow -- reads as no keypoints)
                 ctx.keypoint_stereo(disp[:n], self.q_kp[:n], self.q_cnt[:n], self.K, self.baseline,
                                     out=self.kstereo[:n])
         if self.overlap_sgbm:
@@ -241,8 +276,12 @@ class StereoFrontEnd:
         # but the PnP transforms) is in place before PnP, and the BA's birth counting starts on a
         # side stream right away
         births = self._ba_births(n, kp, m, nm) if self.ba_window else None  # (None without births_ahead)
-        P3, p2, npts = ctx.backproject(disp, self.q_kp[:n], kp[:n], m[:n], nm[:n], self.K, self.baseline,
-                                       out=(self.P3[:n], self.p2[:n], self.npts[:n]))
+        if self.sparse:
+            P3, p2, npts = ctx.backproject_stereo(self.q_stereo[:n], kp[:n], m[:n], nm[:n],
+                                                  out=(self.P3[:n], self.p2[:n], self.npts[:n]))
+        else:
+            P3, p2, npts = ctx.backproject(disp, self.q_kp[:n], kp[:n], m[:n], nm[:n], self.K, self.baseline,
+                                           out=(self.P3[:n], self.p2[:n], self.npts[:n]))
         rv, tv, T, st, _ = ctx.pnp_ransac(P3, p2, npts, self.K, self.dist,
                                           out=(self.rvec[:n], self.tvec[:n], self.T[:n], self.status[:n],
                                                self.inl[:n]))
@@ -273,6 +312,8 @@ class StereoFrontEnd:
         self.disp is one of two slots; with overlap_sgbm the front stage of step k+2 overwrites it
         after waiting for main_done[slot], recorded at the end of step() -- before these launches
         -- so it is recorded again behind them (not under capture, where step() records none)."""
+        if self.sparse:
+            raise RuntimeError('append_dense: depth="sparse" computes no disparity map')
         n = int(cum.shape[0])
         if self.k == 0 or n > self.B:
             raise RuntimeError("append_dense: call it after step(), with that step's n poses")
@@ -280,6 +321,14 @@ class StereoFrontEnd:
         if self.overlap_sgbm and not torch.cuda.is_current_stream_capturing():
             self.main_done[(self.k - 1) % 2] = torch.cuda.current_stream(self.dev).record_event()
         return n_added
+
+    def _sparse_stereo(self, imgs, kp, desc, cnt, n, out):
+        """fvo_sparse_stereo of n pairs laid out as ORB's batch (left images / sets [:n], right
+        [n:2n]) into out [n,cap,4], on the current stream.  (A negative count -- ORB overflow --
+        reads as no keypoints.)"""
+        self.ctx.sparse_stereo(imgs[:n], imgs[n:2 * n], kp[:n], cnt[:n], desc[:n], kp[n:2 * n], cnt[n:2 * n],
+                               desc[n:2 * n], self.K, self.baseline, params=self.sparse_params,
+                               level_scale=self.level_scale, workspace=self.sparse_ws, out=out)
 
     def _sgbm(self, n):
         """SGBM of the step's previous pairs, then the speckle filter when it is enabled
@@ -304,6 +353,7 @@ class StereoFrontEnd:
         self.disp = self.disp_buf[slot]
         self.sg_status = self.sg_status_buf[slot]
         self.kstereo = self.kstereo_buf[slot]
+        self.q_stereo = self.q_stereo_buf[slot] if self.sparse else None
 
     def _ba_births(self, n, kp, m, nm):
         """The step's frames into the BA history (keypoints, matches, stereo points; the PnP

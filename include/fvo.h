@@ -499,6 +499,60 @@ int fvo_reproject_to_3d(fvo_ctx* ctx, const void* disparity, int32_t is_float32,
                         int32_t width, int64_t image_stride, int32_t pitch, const double* Q,
                         int32_t handle_missing_values, uint32_t* min_key, float* out, fvo_stream stream);
 
+/* Sparse stereo (any stage; specification: tests/sparse_stereo_ref.py): the stereo point of every
+ * left keypoint from a left-right ORB match on its own row band, refined to sub-pixel by a SAD
+ * search on the level-0 images, as the per-keypoint record of fvo_keypoint_stereo -- without a
+ * disparity map.  All float arithmetic is float32 in the order written here.
+ * Right keypoint j is a candidate of left keypoint i iff both octaves (record field 5) are
+ * integers in [0, n_levels), fabsf(yR - yL) <= row_tol * level_scale[oL], |oR - oL| <=
+ * max_octave_diff and min_disparity <= xL - xR <= max_disparity.  The best candidate is the
+ * minimum of (hamming << 16) | j, accepted iff hamming <= max_hamming (else status 1).  With
+ * unique != 0, of the left keypoints whose accepted best candidate is j only the one with the
+ * smallest (hamming << 16) | i keeps it (the others: status 2), before the refinement.
+ * Refinement: xl = floorf(xL + 0.5f), yl and xr likewise; the (2w+1)^2 window around (xl, yl) and
+ * the 2S+1 windows around (xr + k, yl), |k| <= S, must lie inside the image (else status 3);
+ * SAD(k) over the window, k* its first minimum; k* = +-S: status 4; delta = (float)(d1 - d3) /
+ * (float)(2 (d1 + d3 - 2 d2)) over SAD(k* - 1), SAD(k*), SAD(k* + 1); d = xL - ((float)(xr + k*) +
+ * delta); d outside [min_disparity, max_disparity]: status 5; Z = (float)(K[0] baseline) / d with
+ * X, Y as fvo_backproject at (xL, yL); 0.1 < Z < 1000 failing: status 6.
+ * left/right:  u8 image b at + b*image_stride, rows `pitch` bytes apart, the context's size.
+ * kpL/kpR:     [batch][cap][8] records, nL/nR [batch] counts (<= 0: empty, > cap: clamped),
+ *              descL/descR [batch][cap][32] (16-byte aligned).  cap in [1, 65535].
+ * level_scale: host float[n_levels], n_levels in [1, 32].  K: host double[9]; baseline in metres.
+ * workspace:   device scratch of fvo_sparse_stereo_workspace_bytes(batch, cap) bytes (caller-owned,
+ *              4-byte aligned, needs no clearing: the call's first kernel initialises it).
+ * stereo:      [batch][cap][4] f32 (X, Y, Z, d), 16-byte aligned; zeros for every status != 0.
+ * info:        [batch][cap][4] i32 or NULL: (right index, hamming, k*, status); right index and
+ *              hamming are -1 under status 1, k* is 0 under statuses 1-3.
+ * Rows >= the left count are not written.  Nothing is allocated; three launches that are not in
+ * the fvo_timing_* table. */
+typedef struct fvo_sparse_stereo_params {
+  float min_disparity;     /* 1.0: finite, > 0 */
+  float max_disparity;     /* 96.0: >= min_disparity */
+  float row_tol;           /* 2.0: finite, >= 0 */
+  int32_t max_hamming;     /* 75: [0, 256] */
+  int32_t max_octave_diff; /* 1: >= 0 */
+  int32_t half_window;     /* 5: w in [1, 7] */
+  int32_t half_slide;      /* 5: S in [1, 8] */
+  int32_t unique;          /* 1 */
+} fvo_sparse_stereo_params;
+void fvo_sparse_stereo_params_default(fvo_sparse_stereo_params* params);
+int64_t fvo_sparse_stereo_workspace_bytes(int32_t batch, int32_t cap);
+int fvo_sparse_stereo(fvo_ctx* ctx, const uint8_t* left, const uint8_t* right, int32_t batch, int64_t image_stride,
+                      int32_t pitch, const float* kpL, const int32_t* nL, const uint8_t* descL, const float* kpR,
+                      const int32_t* nR, const uint8_t* descR, int32_t cap, const fvo_sparse_stereo_params* params,
+                      const float* level_scale, int32_t n_levels, const double* K, double baseline, void* workspace,
+                      int64_t workspace_bytes, float* stereo, int32_t* info, fvo_stream stream);
+
+/* fvo_backproject with the depth taken from the stereo record (fvo_sparse_stereo or
+ * fvo_keypoint_stereo, [batch][cap][4]) of the match's query keypoint: a match is kept iff the
+ * record's Z != 0, points3d = its (X, Y, Z), compacted in match order; nothing is written past
+ * n_points.  kp0 is not read (the record holds the point; the argument keeps fvo_backproject's
+ * shape) and may be NULL.  Any stage. */
+int fvo_backproject_stereo(fvo_ctx* ctx, const float* stereo, const float* kp0, const float* kp1,
+                           const int32_t* matches, const int32_t* n_matches, int32_t batch, int32_t cap,
+                           float* points3d, float* points2d, int32_t* n_points, fvo_stream stream);
+
 /* Test hook: KeyPointsFilter::retainBest on `n` float responses (device memory) with the
  * product's selection kernel.  idx_out [n] receives the surviving original indices in
  * OpenCV's output order, *n_out the survivor count.  Allocates (stream-ordered). */
