@@ -1549,7 +1549,8 @@ int ba_init(fvo_ctx* ctx) {
   FVO_HIP(ctx, hipStreamCreateWithFlags(&ctx->ba_s2, hipStreamNonBlocking));
   FVO_HIP(ctx, hipEventCreateWithFlags(&ctx->ba_fork, hipEventDisableTiming));
   FVO_HIP(ctx, hipEventCreateWithFlags(&ctx->ba_join, hipEventDisableTiming));
-  // dynamic LDS above 64 KiB: the MFMA slice always, the reduced system for K > 11, the match maps
+  // dynamic LDS above 64 KiB: the MFMA slice always, the reduced system for K > 14 (64768 B at K = 12..14,
+  // 89984 B from K = 15), the match maps
   if (build_shm(d) > 65536) {
     const bool g = build_gmap(d);
     FVO_HIP(ctx, hipFuncSetAttribute(g ? (const void*)k_ba_births<true> : (const void*)k_ba_births<false>,

@@ -242,7 +242,19 @@ int fvo_keypoint_stereo(fvo_ctx* ctx, const int16_t* disparity, const float* key
  *   T_rel [F][16]                               camera f -> camera f+1 (PnP), f < F-1
  * Window w (0 <= w < n_windows) ends at frame e = first_end + w and spans frames
  * max(first_valid, e - ba_window + 1) .. e; windows of fewer than 3 frames copy T_rel.
- * inv_sigma2: host double[nlevels] = 1 / scale_factor^(2*octave) observation weights.
+ * inv_sigma2: host double[n_levels] = 1 / scale_factor^(2*octave) observation weights.  A
+ * keypoint's octave (record field 5, truncated toward zero) is clamped to [0, n_levels - 1]
+ * before the lookup, so an octave outside the table takes the weight of its nearest entry.
+ * Preconditions on the match rows (not checked; an index outside its frame reads or writes out
+ * of bounds): rows r < n_matches[f] hold a query index in [0, n_keypoints[f]) and a train index
+ * in [0, n_keypoints[f+1]), and a query index appears at most once per frame (the forward map
+ * keypoint -> match is written without ordering, so a repeated query index would leave either
+ * row's train index).  Duplicate train indices are allowed (a ratio-test match list without
+ * cross-check): the tracks that share the keypoint all continue through it.
+ * Only frames max(first_valid, first_end - ba_window + 1) .. first_end + n_windows - 1 are read
+ * -- of the last one its keypoints alone, of T_rel the rows of the frames before it -- and only
+ * rows below n_keypoints[f] / n_matches[f] (counts are clamped to [0, cap]); frames outside
+ * [first_valid, first_end + n_windows - 1] and rows beyond the counts may hold anything.
  * Outputs: T_out [n_windows][16] refined camera (e-1) -> camera e transform;
  *          stats [n_windows][6] f64: cost0, cost, landmarks, observations, frames, accepted. */
 int fvo_ba_windows(fvo_ctx* ctx, const float* keypoints, const int32_t* n_keypoints, const int32_t* matches,

@@ -30,6 +30,16 @@ Window ending at frame e: frames s..e (n = e - s + 1 <= K), world = camera s.
     schedule) and the current cost is re-evaluated.  Pose update left-multiplicative on
     SO(3) x R3: R <- Exp(w) R, t <- Exp(w) t + v; landmarks X <- X + dX.
   * solve: landmarks eliminated (Schur complement), reduced pose system by Cholesky.
+  * octaves outside the weight table: fvo_ba_windows receives the weights as a table of n_levels
+    entries and clamps a keypoint's octave to [0, n_levels - 1] before the lookup (csrc/ba.hip
+    k_ba_emit; the float octave is truncated toward zero first, as int() here).  With
+    n_levels=None this module evaluates scale_factor ** (2 octave) for any octave, the behaviour
+    before the clamp was specified; with n_levels given, build_problem / ba_window clamp the same
+    way, and that is the definition for octaves outside the table.
+  * inputs the specification does not define (preconditions of fvo_ba_windows, include/fvo.h):
+    match indices outside [0, n_keypoints) of their frames, and a query index that appears in
+    more than one row of a frame (the forward map nxt would depend on the write order).
+    Duplicate train indices are defined: both tracks continue through the shared keypoint.
 """
 from __future__ import annotations
 
@@ -59,8 +69,9 @@ def stereo_points(kp_xy: np.ndarray, disp16: np.ndarray, K: np.ndarray, baseline
     return np.stack([X, Y, Z], 1).astype(f32), d, valid
 
 
-def build_problem(kps, matches, stereo, rel, lmax=LMAX, omax=OMAX, scale_factor=1.2):
-    """kps: n frames of f32[n_f, >=6] keypoint records (x, y, size, angle, response,
+def build_problem(kps, matches, stereo, rel, lmax=LMAX, omax=OMAX, scale_factor=1.2, n_levels=None):
+    """n_levels: clamp the octaves to [0, n_levels - 1] (module docstring); None = no clamp.
+    kps: n frames of f32[n_f, >=6] keypoint records (x, y, size, angle, response,
     octave, ...); matches: n-1 int[M, 3] (L_j -> L_{j+1});
     stereo: n-1 (P f32[n_j,3], d f32[n_j], valid) for the frames with forward matches;
     rel: f64[n-1, 4, 4] camera j -> camera j+1.  Returns (T0 f64[n,4,4], X f64[L,3],
@@ -105,7 +116,10 @@ def build_problem(kps, matches, stereo, rel, lmax=LMAX, omax=OMAX, scale_factor=
                 o_u.append(float(kps[ff][kk, 0]))
                 o_v.append(float(kps[ff][kk, 1]))
                 o_ur.append(float(np.float32(kps[j][q, 0]) - d[q]) if k == 0 else np.nan)
-                o_is.append(1.0 / (scale_factor ** (2 * int(kps[ff][kk, 5]))))
+                octave = int(kps[ff][kk, 5])
+                if n_levels is not None:
+                    octave = min(max(octave, 0), n_levels - 1)
+                o_is.append(1.0 / (scale_factor ** (2 * octave)))
         if stop:
             break
     obs = dict(lm=np.array(o_lm, np.int64), frame=np.array(o_f, np.int64), u=np.array(o_u),
@@ -185,7 +199,7 @@ def _reject(T, X, obs, cam, baseline):
     return out
 
 
-def _solve(T, X, obs, lin, lam, n):
+def _solve(T, X, obs, lin, lam, n, reverse=False):
     cost, r, w, Jp, Jl = lin
     L = len(X)
     Hpp = np.zeros((n, 6, 6))
@@ -208,7 +222,7 @@ def _solve(T, X, obs, lin, lam, n):
         S[6 * (j - 1):6 * j, 6 * (j - 1):6 * j] = Hpp_d[j]
         rhs[6 * (j - 1):6 * j] = -gp[j]
     # Schur complement: S -= sum_l W_l Hll^-1 W_l^T ; rhs += W_l Hll^-1 g_l
-    for l in range(L):
+    for l in (range(L - 1, -1, -1) if reverse else range(L)):
         idx = np.nonzero(obs["lm"] == l)[0]
         fr = obs["frame"][idx]
         keep = fr > 0
@@ -242,32 +256,74 @@ def _apply(T, X, dpf, dX):
     return T2, X + dX
 
 
-def ba_window(kps, matches, stereo, rel, K, baseline, iters=10, lmax=LMAX, omax=OMAX, scale_factor=1.2):
+def _reject_margin(T, X, obs, cam, baseline):
+    """How far _reject's decisions are from their threshold at the current estimate:
+    (min |s - delta^2| / delta^2 over the observations with camera depth > MIN_Z, the number of
+    observations with depth <= MIN_Z)."""
+    fx, fy, cx, cy = cam
+    R = T[obs["frame"], :3, :3]
+    t = T[obs["frame"], :3, 3]
+    Xc = np.einsum("nij,nj->ni", R, X[obs["lm"]]) + t
+    x, y, z = Xc[:, 0], Xc[:, 1], Xc[:, 2]
+    ok = z > MIN_Z
+    iz = 1.0 / np.where(ok, z, 1.0)
+    st = ~np.isnan(obs["ur"])
+    r0 = fx * x * iz + cx - obs["u"]
+    r1 = fy * y * iz + cy - obs["v"]
+    r2 = np.where(st, fx * (x - baseline) * iz + cx - np.nan_to_num(obs["ur"]), 0.0)
+    s = (r0 * r0 + r1 * r1 + r2 * r2) * obs["isig2"]
+    d2 = np.where(st, D2_STEREO, D2_MONO)
+    m = (np.abs(s - d2) / d2)[ok]
+    return (float(m.min()) if len(m) else float("inf")), int((~ok).sum())
+
+
+def _reorder(obs):
+    """The observations of every landmark in reverse order (same problem, another summation order)."""
+    idx = np.lexsort((-np.arange(len(obs["lm"])), obs["lm"]))
+    return {k: v[idx] for k, v in obs.items()}
+
+
+def ba_window(kps, matches, stereo, rel, K, baseline, iters=10, lmax=LMAX, omax=OMAX, scale_factor=1.2,
+              n_levels=None, reorder=False):
     """Windowed LM bundle adjustment (module docstring).  Returns dict with refined poses
     T f64[n,4,4] (world = first camera), rel f64[n-1,4,4] refined relative transforms,
-    X f64[L,3], obs, cost0, cost, accepted (number of accepted steps)."""
-    T, X, obs = build_problem(kps, matches, stereo, rel, lmax, omax, scale_factor)
+    X f64[L,3], obs, cost0, cost, accepted (number of accepted steps) and trace, one dict per LM
+    iteration: lam (before the solve), cost (the current cost the step is judged against), c2 (the
+    tentative cost, None when the Cholesky factorisation failed), accepted, and at the rejection
+    iteration reject_margin / n_behind (_reject_margin).  reorder=True sums in another order
+    (observations reversed within each landmark, the Schur loop over the landmarks backwards): the
+    same mathematics, used by the tests to measure this module's own rounding sensitivity."""
+    T, X, obs = build_problem(kps, matches, stereo, rel, lmax, omax, scale_factor, n_levels)
+    if reorder:
+        obs = _reorder(obs)
     n = len(kps)
     cam = (float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]))
     lam = LAM0
     cost0 = cost = _linearize(T, X, obs, cam, baseline, need_jac=False) if len(X) else 0.0
     accepted = 0
+    trace = []
     for it in range(iters if len(X) else 0):
+        tr = dict(lam=lam)
+        trace.append(tr)
         if it == iters // 2 and iters >= 2:
+            tr["reject_margin"], tr["n_behind"] = _reject_margin(T, X, obs, cam, baseline)
             obs = _reject(T, X, obs, cam, baseline)
             cost = _linearize(T, X, obs, cam, baseline, need_jac=False)
+        tr.update(cost=cost, c2=None, accepted=False)
         lin = _linearize(T, X, obs, cam, baseline)
-        step = _solve(T, X, obs, lin, lam, n)
+        step = _solve(T, X, obs, lin, lam, n, reverse=reorder)
         if step is None:
             lam = min(lam * 10, 1e7)
             continue
         T2, X2 = _apply(T, X, *step)
         c2 = _linearize(T2, X2, obs, cam, baseline, need_jac=False)
+        tr["c2"] = c2
         if c2 < cost:
             T, X, cost = T2, X2, c2
             lam = max(lam / 10, 1e-7)
             accepted += 1
+            tr["accepted"] = True
         else:
             lam = min(lam * 10, 1e7)
     relr = np.array([T[j + 1] @ np.linalg.inv(T[j]) for j in range(n - 1)]).reshape(-1, 4, 4)
-    return dict(T=T, rel=relr, X=X, obs=obs, cost0=cost0, cost=cost, accepted=accepted)
+    return dict(T=T, rel=relr, X=X, obs=obs, cost0=cost0, cost=cost, accepted=accepted, trace=trace)
