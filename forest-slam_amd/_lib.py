@@ -92,6 +92,11 @@ SIGNATURES = {
     "fvo_count_guard": (ctypes.c_int, [_P, _P, _P, _I, _I, _P, _I, _P, _P]),
     "fvo_voxel_workspace_bytes": (ctypes.c_int64, [_L]),
     "fvo_voxel_down_sample": (ctypes.c_int, [_P, _P, _L, ctypes.c_double, _P, _L, _P, _P, _P, _P]),
+    "fvo_outlier_workspace_bytes": (ctypes.c_int64, [_L, _I]),
+    "fvo_statistical_outliers": (ctypes.c_int, [_P, _P, _L, _I, ctypes.c_double, ctypes.c_double, _I, _P, _L, _P, _P,
+                                                _P, _P, _P]),
+    "fvo_radius_outliers": (ctypes.c_int, [_P, _P, _L, _I, ctypes.c_double, ctypes.c_double, _P, _L, _P, _P, _P, _P]),
+    "fvo_select_points": (ctypes.c_int, [_P, _P, _L, _P, _P, _P, _P, _P]),
     "fvo_speckle_workspace_bytes": (ctypes.c_int64, [_I, _I, _I]),
     "fvo_filter_speckles": (ctypes.c_int, [_P, _P, _I, _I, _I, _L, _I, _I, _I, _I, _P, _L, _P]),
     "fvo_dense_workspace_bytes": (ctypes.c_int64, [_I, _I, _I, _I]),
@@ -639,6 +644,79 @@ class Context:
         self._check(self.L.fvo_voxel_down_sample(self.h, _ptr(points), n, float(voxel_size), _ptr(workspace), wb,
                                                  _ptr(out), _ptr(cnt), _ptr(status), _stream(self.device)))
         return out, cnt, status
+
+    def outlier_workspace_bytes(self, n_points: int, nb_neighbors: int = 1) -> int:
+        """fvo_outlier_workspace_bytes: scratch bytes of statistical_outliers / radius_outliers."""
+        wb = int(self.L.fvo_outlier_workspace_bytes(int(n_points), int(nb_neighbors)))
+        if wb < 0:
+            raise ValueError(f"outlier removal: unsupported size n_points={n_points} nb_neighbors={nb_neighbors}")
+        return wb
+
+    def _outlier_args(self, points, workspace, nb_neighbors, name):
+        if points.dtype != torch.float64 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
+            raise TypeError(f"{name}: points must be a contiguous float64 [N, 3] tensor")
+        n = points.shape[0]
+        wb = self.outlier_workspace_bytes(n, nb_neighbors)
+        if workspace is None:
+            workspace = torch.empty((max(wb, 8),), dtype=torch.uint8, device=self.device)
+        elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < wb:
+            raise ValueError(f"{name}: workspace must be a contiguous uint8 tensor of >= {wb} bytes")
+        return n, workspace
+
+    def statistical_outliers(self, points, nb_neighbors=20, std_ratio=2.0, cell=1.0, max_rings=2, workspace=None,
+                             avg_distance=True, status=True):
+        """Open3D remove_statistical_outlier's mask (fvo_statistical_outliers; the rule:
+        tests/outlier_ref.py): points f64 [N,3] (device, not modified) -> (keep u8 [N], avg_distance
+        f64 [N] or None, stats f64 [6] = mean, std, threshold, valid, kept, queries finished by the
+        exact pass, status i32 [1] or None: 1 = a cell index outside the 21-bit range or a non-finite
+        coordinate).  cell and max_rings change the time only.  workspace: uint8 device tensor of >=
+        outlier_workspace_bytes(N, nb_neighbors) bytes, allocated here only when none is passed;
+        avg_distance / status False: that output is not requested (NULL)."""
+        n, workspace = self._outlier_args(points, workspace, nb_neighbors, "statistical_outliers")
+        keep = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        avg = torch.empty((n,), dtype=torch.float64, device=self.device) if avg_distance else None
+        stats = torch.empty((6,), dtype=torch.float64, device=self.device)
+        st = torch.empty((1,), dtype=torch.int32, device=self.device) if status else None
+        self._check(self.L.fvo_statistical_outliers(self.h, _ptr(points), n, int(nb_neighbors), float(std_ratio),
+                                                    float(cell), int(max_rings), _ptr(workspace), workspace.numel(),
+                                                    _ptr(keep), _ptr(avg), _ptr(stats), _ptr(st),
+                                                    _stream(self.device)))
+        return keep, avg, stats, st
+
+    def radius_outliers(self, points, nb_points, radius, cell=None, workspace=None, n_neighbors=True, status=True):
+        """Open3D remove_radius_outlier's mask (fvo_radius_outliers): points f64 [N,3] (device) ->
+        (keep u8 [N], n_neighbors i32 [N] or None: the points with d2 < radius^2, the query included,
+        status i32 [1] or None).  cell None = radius; radius / cell <= 8."""
+        n, workspace = self._outlier_args(points, workspace, 1, "radius_outliers")
+        keep = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        cnt = torch.empty((n,), dtype=torch.int32, device=self.device) if n_neighbors else None
+        st = torch.empty((1,), dtype=torch.int32, device=self.device) if status else None
+        self._check(self.L.fvo_radius_outliers(self.h, _ptr(points), n, int(nb_points), float(radius),
+                                               float(radius if cell is None else cell), _ptr(workspace),
+                                               workspace.numel(), _ptr(keep), _ptr(cnt), _ptr(st),
+                                               _stream(self.device)))
+        return keep, cnt, st
+
+    def select_points(self, points, keep, out64=None, out32=None, n_out=None):
+        """The points with keep != 0 in input order (fvo_select_points): points f64 [N,3], keep u8 [N]
+        (device) -> (out64 f64 [N,3] or None, out32 f32 [N,3] or None, n_out i32 [1]); the first n_out
+        rows are written, nothing past them.  With neither output given both are allocated."""
+        if points.dtype != torch.float64 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
+            raise TypeError("select_points: points must be a contiguous float64 [N, 3] tensor")
+        n = points.shape[0]
+        if keep.dtype != torch.uint8 or keep.numel() != n or not keep.is_contiguous():
+            raise TypeError("select_points: keep must be a contiguous uint8 [N] tensor")
+        if out64 is None and out32 is None:
+            out64 = torch.empty((max(n, 1), 3), dtype=torch.float64, device=self.device)  # n = 0: not NULL
+            out32 = torch.empty((max(n, 1), 3), dtype=torch.float32, device=self.device)
+        for o, dt in ((out64, torch.float64), (out32, torch.float32)):
+            if o is not None and (o.dtype != dt or o.numel() < 3 * n or not o.is_contiguous()):
+                raise TypeError(f"select_points: outputs must be contiguous {dt} tensors of >= N rows")
+        if n_out is None:
+            n_out = torch.empty((1,), dtype=torch.int32, device=self.device)
+        self._check(self.L.fvo_select_points(self.h, _ptr(points), n, _ptr(keep), _ptr(out64), _ptr(out32),
+                                             _ptr(n_out), _stream(self.device)))
+        return out64, out32, n_out
 
     def speckle_workspace_bytes(self, batch: int, height: int, width: int) -> int:
         """fvo_speckle_workspace_bytes: scratch bytes of filter_speckles for [batch, height, width]."""

@@ -302,6 +302,17 @@ int sparse_stereo_run(fvo_ctx* ctx, const uint8_t* left, const uint8_t* right, i
 int backproject_stereo_run(fvo_ctx* ctx, const float* stereo, const float* kp1, const int32_t* matches,
                            const int32_t* nmatch, int batch, int cap, float* P3, float* p2, int32_t* npts,
                            hipStream_t s);
+// Outlier removal (outlier.hip).  capi_outlier.cpp validates the arguments.  ws: the grid's sorted
+// keys, the points in that order, the averages, the exact pass's list and the sums' partials
+// (fvo_outlier_workspace_bytes; the top-k lists are in LDS, so the size does not depend on k).
+int64_t outlier_workspace_bytes(int64_t n);
+int statistical_outliers_run(fvo_ctx* ctx, const double* pts, int64_t n, int nb_neighbors, double std_ratio,
+                             double cell, int max_rings, void* ws, uint8_t* keep, double* avg_distance, double* stats,
+                             int32_t* status, hipStream_t s);
+int radius_outliers_run(fvo_ctx* ctx, const double* pts, int64_t n, int nb_points, double radius, double cell,
+                        void* ws, uint8_t* keep, int32_t* n_neighbors, int32_t* status, hipStream_t s);
+int select_points_run(fvo_ctx* ctx, const double* pts, int64_t n, const uint8_t* keep, double* out64, float* out32,
+                      int32_t* n_out, hipStream_t s);
 int mono_init(fvo_ctx* ctx);
 int gather_run(fvo_ctx* ctx, const float* kp0, const float* kp1, const int32_t* matches, const int32_t* nmatch,
                int batch, int cap, float* p0, float* p1, int32_t* npts, hipStream_t s);

@@ -9,6 +9,8 @@ fvo_voxel_down_sample.
   transformed by the pose, ``voxel_down_sample(voxel_size=0.5)``, appended to the map.
 * ``PointMap.add_disparity`` — dense stereo mapping over fvo_dense_map_append (no reference
   counterpart): whole disparity maps back-projected and appended, optionally voxel-filtered.
+* ``PointMap.remove_statistical_outlier`` / ``remove_radius_outlier`` — Open3D's map clean-up
+  (fvo_statistical_outliers, fvo_radius_outliers, fvo_select_points) on the device, in place.
 
 The map lives in HBM (fp64 + the float32 record), sized once; the append offset is a device
 counter, so batches append without host synchronisation."""
@@ -31,6 +33,7 @@ class PointMap:
         self._tmp64 = None
         self._ws = None
         self._dense_ws = None
+        self._ol_ws = None
 
     def __len__(self) -> int:
         n = int(self.count.item())
@@ -130,6 +133,50 @@ class PointMap:
         self.xyz32[base:base + k] = out[:k].to(torch.float32)
         self.count += k
         return n_added
+
+    def _apply_mask(self, n: int, keep: torch.Tensor) -> torch.Tensor:
+        """Compact the first n points by the u8 mask, in place through a scratch copy, keeping the
+        order; returns the kept indices (int64, device)."""
+        src = self.xyz64[:n].clone()
+        self.ctx.select_points(src, keep, self.xyz64, self.xyz32, self.count)
+        return torch.nonzero(keep).reshape(-1)
+
+    def _outlier_ws(self, n: int, nb_neighbors: int) -> torch.Tensor:
+        wb = self.ctx.outlier_workspace_bytes(n, nb_neighbors)
+        if self._ol_ws is None or self._ol_ws.numel() < wb:
+            self._ol_ws = torch.empty((max(wb, 8),), dtype=torch.uint8, device=self.dev)
+        return self._ol_ws
+
+    def remove_statistical_outlier(self, nb_neighbors: int = 20, std_ratio: float = 2.0, cell: float = 1.0,
+                                   max_rings: int = 2) -> torch.Tensor:
+        """Open3D ``remove_statistical_outlier(nb_neighbors, std_ratio)`` on the map, in place: the
+        points whose mean distance to their nb_neighbors nearest (themselves included) is > 0 and
+        below mean + std_ratio * std stay, in order.  cell (metres) and max_rings tune the search
+        only.  Returns the kept indices (Open3D's ``ind``) as an int64 device tensor (host sync)."""
+        n = len(self)
+        if n == 0:
+            return torch.zeros((0,), dtype=torch.int64, device=self.dev)
+        keep, _, _, st = self.ctx.statistical_outliers(self.xyz64[:n], nb_neighbors, std_ratio, cell, max_rings,
+                                                       workspace=self._outlier_ws(n, nb_neighbors),
+                                                       avg_distance=False)
+        if int(st.item()) != 0:
+            raise RuntimeError("remove_statistical_outlier: cell index outside the 21-bit key range or a "
+                               "non-finite coordinate")
+        return self._apply_mask(n, keep)
+
+    def remove_radius_outlier(self, nb_points: int, radius: float, cell: float | None = None) -> torch.Tensor:
+        """Open3D ``remove_radius_outlier(nb_points, radius)`` on the map, in place: the points with
+        more than nb_points points (themselves included) closer than radius stay, in order.
+        cell None = radius.  Returns the kept indices as an int64 device tensor (host sync)."""
+        n = len(self)
+        if n == 0:
+            return torch.zeros((0,), dtype=torch.int64, device=self.dev)
+        keep, _, st = self.ctx.radius_outliers(self.xyz64[:n], nb_points, radius, cell,
+                                               workspace=self._outlier_ws(n, 1), n_neighbors=False)
+        if int(st.item()) != 0:
+            raise RuntimeError("remove_radius_outlier: cell index outside the 21-bit key range or a "
+                               "non-finite coordinate")
+        return self._apply_mask(n, keep)
 
     def cloud32(self) -> np.ndarray:
         return self.xyz32[: len(self)].cpu().numpy()

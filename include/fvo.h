@@ -37,6 +37,10 @@
  *                              float32 packing: stereo_slam.py:308-318; mono_slam.py:148; gt_mapping.py
  *   fvo_voxel_down_sample   <- open3d PointCloud.voxel_down_sample(voxel_size=0.5)
  *                              mono_slam.py:151-155, gt_mapping.py:62-66
+ *   fvo_statistical_outliers <- open3d PointCloud.remove_statistical_outlier(nb_neighbors, std_ratio)
+ *   fvo_radius_outliers     <- open3d PointCloud.remove_radius_outlier(nb_points, radius)
+ *   fvo_select_points       <- open3d PointCloud.select_by_index(ind) of the kept points, in order
+ *                              (the map clean-up after voxel_down_sample; no reference counterpart)
  *   fvo_filter_speckles     <- cv2.filterSpeckles / StereoSGBM_create(speckleWindowSize=, speckleRange=)
  *   fvo_dense_map_append    <- (new) the disparity maps of a batch as one world-frame point cloud: the
  *                              back-projection of stereo_slam.py:262-289 at every step-th pixel + the
@@ -447,6 +451,53 @@ int fvo_count_guard(fvo_ctx* ctx, const int32_t* counts, const int32_t* q_counts
 int64_t fvo_voxel_workspace_bytes(int64_t n_points);
 int fvo_voxel_down_sample(fvo_ctx* ctx, const double* points, int64_t n_points, double voxel_size, void* workspace,
                           int64_t workspace_bytes, double* out, int32_t* n_out, int32_t* status, fvo_stream stream);
+
+/* Open3D PointCloud::RemoveStatisticalOutliers / RemoveRadiusOutliers (0.17, restated; any stage,
+ * no context workspace) on n_points fp64 xyz points (device [n][3], not modified), and the
+ * selection of the kept points.  Specification: tests/outlier_ref.py.  All arithmetic is fp64 in
+ * the order written here; d2(i, j) = ((dx*dx + dy*dy) + dz*dz) with dx = p_j.x - p_i.x.
+ * Statistical: k = min(nb_neighbors, n); point i's neighbours are the k smallest d2(i, j) over all
+ * j in [0, n), j = i included (the KD-tree returns the query at distance 0); avg_i = (((0 +
+ * sqrt(d2_(0))) + sqrt(d2_(1))) + ...) / (double)k in ascending order of d2; mean = sum of the
+ * avg_i > 0 over n, std = sqrt(sum of (avg_i - mean)^2 over the avg_i > 0, over n - 1), threshold =
+ * mean + std_ratio * std; keep[i] = avg_i > 0 && avg_i < threshold.  A point whose k nearest all
+ * coincide with it (avg = 0) is dropped and is in neither sum; with n = 1 std is 0/0 and nothing
+ * is kept.  avg_distance, keep and stats[3..5] are exact; the two sums are deterministic (fixed
+ * order, no floating-point atomics, serial chains of <= 4096 terms), so stats[0..2] repeat bit
+ * for bit and differ from a correctly rounded sum by ~1e-12 relative at most.
+ * Radius: count_i = #{ j : d2(i, j) < radius*radius } (strict, j = i included), keep[i] =
+ * count_i > nb_points.
+ * Both search a uniform grid of side `cell` (origin: the min bound; keys as
+ * fvo_voxel_down_sample's): cell and max_rings change the time only, never a result.  The
+ * statistical search visits the cells at Chebyshev distance 0 .. max_rings of the query's own and
+ * finishes the queries it cannot prove complete there (true flyers) by a brute-force pass over
+ * all n points, which gives the same bits; the radius search visits ceil(radius / cell) + 1 rings,
+ * so radius / cell > 8 is refused.
+ * workspace: device scratch of fvo_outlier_workspace_bytes(n_points, nb_neighbors) bytes
+ *            (nb_neighbors = 1 for the radius call; caller-owned, 8-byte aligned, needs no clearing
+ *            between calls); that function returns -1 for a refused size.
+ * keep:      device [n] u8, 1 = kept.  avg_distance: device [n] or NULL.  n_neighbors: [n] or NULL.
+ * stats:     device double[6]: mean, std, threshold, valid (= n), kept, queries finished by the
+ *            brute-force pass.
+ * status (device, may be NULL): 0 ok, 1 = a cell index outside [0, 2^21) or a non-finite
+ *            coordinate (every result invalid).
+ * fvo_select_points: out64 / out32 (one may be NULL) receive the points with keep[i] != 0 in input
+ * order, as fp64 rows and / or their float32 casts, *n_out (device) their number; nothing is
+ * written past it.  Neither output may overlap points.
+ * n_points == 0 returns 0 after the argument checks (points, workspace and keep may then be NULL;
+ * stats and *n_out are zeroed).  Nothing is allocated; the calls are stream-ordered and can be
+ * captured into a hipGraph; their launches are not in the fvo_timing_* table. */
+#define FVO_OUTLIER_MAX_K 64
+int64_t fvo_outlier_workspace_bytes(int64_t n_points, int32_t nb_neighbors);
+int fvo_statistical_outliers(fvo_ctx* ctx, const double* points, int64_t n_points, int32_t nb_neighbors,
+                             double std_ratio, double cell, int32_t max_rings, void* workspace,
+                             int64_t workspace_bytes, uint8_t* keep, double* avg_distance, double* stats,
+                             int32_t* status, fvo_stream stream);
+int fvo_radius_outliers(fvo_ctx* ctx, const double* points, int64_t n_points, int32_t nb_points, double radius,
+                        double cell, void* workspace, int64_t workspace_bytes, uint8_t* keep, int32_t* n_neighbors,
+                        int32_t* status, fvo_stream stream);
+int fvo_select_points(fvo_ctx* ctx, const double* points, int64_t n_points, const uint8_t* keep, double* out64,
+                      float* out32, int32_t* n_out, fvo_stream stream);
 
 /* cv2.filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) on `batch` CV_16SC1 disparity maps, in
  * place (any stage; any image size, not tied to the context's).  Two 4-neighbours are connected
