@@ -676,7 +676,8 @@ int fvo_timing_read(fvo_ctx* c, double* ms, int32_t* launches) {
 //        3 per-level candidate counts, 4 after retainBest(2n), 5 after retainBest(n) (i32 [B][L]),
 //        6 PnP RANSAC inlier count per iteration (i32 [B][1000]), 7 PnP hypotheses (f64 [B][1000][6]),
 //        8 PnP RANSAC state (i32 [B][4]: best inlier count, iteration bound, best iteration, points),
-//        9 SGBM control words, 10 no buffer (0 bytes): ORB orientation as a separate pass from now on.
+//        9 SGBM control words, 10 no buffer (0 bytes): ORB orientation as a separate pass from now on,
+//        11 SGBM raw disparity (before the median) of the last call's last chunk of pairs.
 int fvo_debug_buffer(fvo_ctx* c, int which, void** ptr, int64_t* bytes) {
   if (!c || !ptr || !bytes) return -1;
   const int64_t B = c->cfg.max_batch;
@@ -705,6 +706,11 @@ int fvo_debug_buffer(fvo_ctx* c, int which, void** ptr, int64_t* bytes) {
       if (!c->pyr) return fvo_fail(c, "orb stage not enabled");
       c->g.angle_pass = true;
       *ptr = nullptr; *bytes = 0; return 0;
+    case 11: {  // SGBM's disparity before the median, i16 [sgbm batch][H][W] (sgbm_init's allocation)
+      if (!c->sg_raw) return fvo_fail(c, "no SGBM workspace");
+      const int64_t sb = c->cfg.sgbm_max_batch > 0 ? std::min<int64_t>(c->cfg.sgbm_max_batch, B) : B;
+      *ptr = c->sg_raw; *bytes = sb * c->cfg.height * c->cfg.width * 2; return 0;
+    }
     default: return fvo_fail(c, "unknown debug buffer");
   }
 }

@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "fvo_device.h"
+#include "sgbm_costmap.h"
 #include "sgbm_params.h"
 
 namespace {
@@ -266,7 +267,8 @@ __device__ __forceinline__ void derive16(const uint32_t* vp, const uint32_t* v, 
 // range in LDS (left: CB+6 px, right: CB+6+D-1 px, +2 apron each side), derives the
 // (x-Sobel, intensity) channel words and their BT min/max, evaluates the packed BT pixel
 // cost of its (CB+6) x D cells into LDS (task slots laid out so neither the BT word reads nor
-// the cost stores conflict on LDS banks) and box-sums 7 columns per lane.  The window's 7
+// the cost stores conflict on LDS banks; a pixel's six BT words are one record, read as three
+// ds_read_b64 -- sgbm_costmap.h) and box-sums 7 columns per lane.  The window's 7
 // hsum rows are a shift register in VGPRs, so the hsum volume never goes to HBM.  The next
 // row's image bytes are loaded right after the current row is staged and taken before the
 // row's C / V stores (vmcnt retires in order: a wait for them behind the stores would also
@@ -297,6 +299,14 @@ typedef __attribute__((address_space(1))) unsigned int sg_gu32;
 // inlined into the cost pass's 7-way unrolled row loop its address arithmetic was hoisted and
 // kept the whole kernel above 128 VGPRs (156 VGPRs / 3 waves per SIMD, or 33 spills at 128).
 typedef __attribute__((address_space(3))) const uint32_t lds_cu32;
+
+// One 8-byte LDS read that stays one ds_read_b64 (2 LDS cycles per wave): volatile, because the
+// compiler pairs neighbouring plain 8-byte reads into ds_read2_b64, which runs at half that rate.
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) const volatile u32x2 lds_cv64;
+__device__ __forceinline__ u32x2 lds_read64(const void* p, int i) { return ((lds_cv64*)p)[i]; }
+// 8-byte reads of the box sum in flight, 2 VGPRs each (all 21 of D = 96, G = 8 at once spill: 128 VGPRs + scratch)
+constexpr int kBoxAhead = 12;
 
 // the granules of rows ya.. (nr rows) of column block kb - 1 from memory: one pass, no waiting
 template <int PQ16>
@@ -431,8 +441,9 @@ __global__ __launch_bounds__(G * CB, LP ? 4 : (G == 16 && D <= 96 ? 6 : (G == 8 
   // per hsum row of a call (two per call in the classic schedule, one under LP)
   constexpr int NRS = LP ? 1 : 2;
   __shared__ uint32_t sCh[NRS][kCX + 2 + NRC + 2];                  // (Sobel, intensity), L then R
-  __shared__ uint32_t sU[NRS][6][kCX];                             // left BT words per channel (splat)
-  __shared__ uint32_t sV[NRS][6][NRC];                             // right BT words per channel (pixel pairs)
+  // BT words, a record of kSgRec words per pixel (sgbm_costmap.h)
+  __shared__ __attribute__((aligned(16))) uint32_t sU[NRS][kCX * kSgRec];  // left: splat words
+  __shared__ __attribute__((aligned(16))) uint32_t sV[NRS][NRC * kSgRec];  // right: (pixel k, pixel k-1) pairs
   __shared__ __attribute__((aligned(16))) uint16_t sPC[NRS][kCX][D];  // pixel cost
   __shared__ uint32_t sRing[LP ? 4 : 1][RW];
   __shared__ int sUnit;
@@ -507,20 +518,17 @@ __global__ __launch_bounds__(G * CB, LP ? 4 : (G == 16 && D <= 96 ? 6 : (G == 8 
     if (hi + 1 <= upto) { load_row(preB, hi + 1); pendB = ++hi; }
   };
   // ---- per-thread pixel-cost tasks (8 disparities of one column each), fixed for the block:
-  // left word index kl, right pair index of the first disparity pair, output offset
-  constexpr int NDB = D / 32;
-  constexpr int NSLOT = ((kCX + 7) / 8) * NDB * 32;
-  constexpr int NTASK = (NSLOT + NT - 1) / NT;
+  // left record, lowest right record and output offset (sg_task, sgbm_costmap.h), the records as
+  // word offsets
+  constexpr int NTASK = sg_ntask(D, CB, NT);
+  static_assert(kCX == sg_kcx(CB) && NRC == sg_nrc(D, CB), "the tile of sgbm_costmap.h");
   int tk_kl[NTASK], tk_jr[NTASK], tk_out[NTASK];
 #pragma unroll
   for (int m = 0; m < NTASK; ++m) {
-    const int t = tid + NT * m;
-    const int g = t >> 5, w = t & 31;
-    const int i = (g / NDB) * 8 + (w >> 2), d0 = ((g % NDB) * 4 + (w & 3)) * 8;
-    const int x1c = min(max(c0 - 3 + i, 0), p.width1 - 1);
-    tk_kl[m] = x1c + p.minX1 - xl0;
-    tk_jr[m] = tk_kl[m] + (D - 1) - d0;  // right pixel of disparity d0 (pairs: d0 + 2j at tk_jr - 2j)
-    tk_out[m] = (t < NSLOT && i < kCX) ? i * D + d0 : -1;
+    const SgTask k = sg_task(tid + NT * m, D, CB, c0, p.width1, p.minX1, xl0);
+    tk_kl[m] = sg_rec(k.kl, 0);
+    tk_jr[m] = sg_rec(k.jr0, 0);  // disparity pair d0 + 2h: record jr0 + 2 (3 - h)
+    tk_out[m] = k.out;
   }
   // hsum rows e .. e + NR - 1 (rows past H - 1 clamp to it) from the ring -> acc0 (, acc1): this
   // lane's column and disparity run.  NR = 2 (classic schedule): two rows per phase, one barrier
@@ -573,19 +581,27 @@ __global__ __launch_bounds__(G * CB, LP ? 4 : (G == 16 && D <= 96 ? 6 : (G == 8 
       btw(ch, k, x, u, mn, mx);
       if (left) {
         const u16x2 w3[3] = {u, mn, mx};
+        uint32_t rec[kSgRec];
 #pragma unroll
         for (int c = 0; c < 2; ++c)
 #pragma unroll
-          for (int e = 0; e < 3; ++e) sU[rr][3 * c + e][k] = as_u(splat(c ? as_u(w3[e]) >> 16 : as_u(w3[e])));
+          for (int e = 0; e < 3; ++e) rec[3 * c + e] = as_u(splat(c ? as_u(w3[e]) >> 16 : as_u(w3[e])));
+        uint2* dst = reinterpret_cast<uint2*>(&sU[rr][sg_rec(k, 0)]);
+#pragma unroll
+        for (int e = 0; e < kSgRec / 2; ++e) dst[e] = make_uint2(rec[2 * e], rec[2 * e + 1]);
       } else if (k > 0) {
         u16x2 up, mnp, mxp;  // the right pixel k - 1
         btw(ch, k - 1, x - 1, up, mnp, mxp);
         const uint32_t a3[3] = {as_u(u), as_u(mn), as_u(mx)}, b3[3] = {as_u(up), as_u(mnp), as_u(mxp)};
+        uint32_t rec[kSgRec];
 #pragma unroll
         for (int e = 0; e < 3; ++e) {
-          sV[rr][e][k] = (a3[e] & 0xFFFFu) | (b3[e] << 16);             // x-Sobel (k, k-1)
-          sV[rr][3 + e][k] = (a3[e] >> 16) | (b3[e] & 0xFFFF0000u);     // intensity (k, k-1)
+          rec[e] = (a3[e] & 0xFFFFu) | (b3[e] << 16);             // x-Sobel (k, k-1)
+          rec[3 + e] = (a3[e] >> 16) | (b3[e] & 0xFFFF0000u);     // intensity (k, k-1)
         }
+        uint2* dst = reinterpret_cast<uint2*>(&sV[rr][sg_rec(k, 0)]);
+#pragma unroll
+        for (int e = 0; e < kSgRec / 2; ++e) dst[e] = make_uint2(rec[2 * e], rec[2 * e + 1]);
       }
     }
     __syncthreads();
@@ -596,18 +612,28 @@ __global__ __launch_bounds__(G * CB, LP ? 4 : (G == 16 && D <= 96 ? 6 : (G == 8 
 #pragma unroll
     for (int m = 0; m < NTASK; ++m) {
       if (tk_out[m] < 0) continue;
-      const int kl = tk_kl[m];
-      u16x2 uu[6];
+      // the task's 15 reads first (volatile reads keep their order): all in flight before the
+      // first use, instead of one record's latency per disparity pair
+      u16x2 uu[kSgRec], vv[4][kSgRec];
 #pragma unroll
-      for (int e = 0; e < 6; ++e) uu[e] = as_v(sU[rr][e][kl]);
+      for (int e = 0; e < kSgRec / 2; ++e) {
+        const u32x2 w2 = lds_read64(&sU[rr][tk_kl[m]], e);
+        uu[2 * e] = as_v(w2.x), uu[2 * e + 1] = as_v(w2.y);
+      }
+#pragma unroll
+      for (int h = 0; h < 4; ++h)
+#pragma unroll
+        for (int e = 0; e < kSgRec / 2; ++e) {
+          const u32x2 w2 = lds_read64(&sV[rr][tk_jr[m] + sg_rec(2 * (3 - h), 0)], e);
+          vv[h][2 * e] = as_v(w2.x), vv[h][2 * e + 1] = as_v(w2.y);
+        }
       uint32_t out[4];
 #pragma unroll
       for (int h = 0; h < 4; ++h) {
-        const int jr = tk_jr[m] - 2 * h;
         u16x2 mc[2];
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-          const u16x2 v = as_v(sV[rr][3 * c][jr]), v0 = as_v(sV[rr][3 * c + 1][jr]), v1 = as_v(sV[rr][3 * c + 2][jr]);
+          const u16x2 v = vv[h][3 * c], v0 = vv[h][3 * c + 1], v1 = vv[h][3 * c + 2];
           const u16x2 u = uu[3 * c], u0 = uu[3 * c + 1], u1 = uu[3 * c + 2];
           const u16x2 cA = __builtin_elementwise_max(__builtin_elementwise_sub_sat(u, v1), __builtin_elementwise_sub_sat(v0, u));
           const u16x2 cB = __builtin_elementwise_max(__builtin_elementwise_sub_sat(v, u1), __builtin_elementwise_sub_sat(u0, v));
@@ -623,18 +649,28 @@ __global__ __launch_bounds__(G * CB, LP ? 4 : (G == 16 && D <= 96 ? 6 : (G == 8 
       uint32_t* acc = rr == 0 ? acc0 : acc1;
 #pragma unroll
       for (int k = 0; k < PQ; ++k) acc[k] = 0;
+      if constexpr (DQ % 4 == 0) {
+        // whole columns of up to kBoxAhead reads ahead of their sums (volatile reads keep their order)
+        constexpr int TC = NV2 * 7 <= kBoxAhead ? 7 : (kBoxAhead / NV2 > 0 ? kBoxAhead / NV2 : 1);
 #pragma unroll
-      for (int t = 0; t < 7; ++t) {
-        if constexpr (DQ % 4 == 0) {
-          const uint2* src = reinterpret_cast<const uint2*>(&sPC[rr][col + t][q * DQ]);
+        for (int t0 = 0; t0 < 7; t0 += TC) {
+          u32x2 w2[TC][NV2];
 #pragma unroll
-          for (int k = 0; k < NV2; ++k) {
-            const uint2 w2 = src[k];
-            acc[2 * k] = as_u(as_v(acc[2 * k]) + as_v(w2.x));
-            acc[2 * k + 1] = as_u(as_v(acc[2 * k + 1]) + as_v(w2.y));
-          }
-        } else {
-          const uint32_t* src = reinterpret_cast<const uint32_t*>(&sPC[rr][col + t][q * DQ]);
+          for (int t = t0; t < t0 + TC && t < 7; ++t)
+#pragma unroll
+            for (int k = 0; k < NV2; ++k) w2[t - t0][k] = lds_read64(&sPC[rr][0][0] + sg_box_run(D, DQ, col, t, q), k);
+#pragma unroll
+          for (int t = t0; t < t0 + TC && t < 7; ++t)
+#pragma unroll
+            for (int k = 0; k < NV2; ++k) {
+              acc[2 * k] = as_u(as_v(acc[2 * k]) + as_v(w2[t - t0][k].x));
+              acc[2 * k + 1] = as_u(as_v(acc[2 * k + 1]) + as_v(w2[t - t0][k].y));
+            }
+        }
+      } else {
+#pragma unroll
+        for (int t = 0; t < 7; ++t) {
+          const uint32_t* src = reinterpret_cast<const uint32_t*>(&sPC[rr][0][0] + sg_box_run(D, DQ, col, t, q));
 #pragma unroll
           for (int k = 0; k < PQ; ++k) acc[k] = as_u(as_v(acc[k]) + as_v(src[k]));
         }
@@ -696,7 +732,6 @@ __global__ __launch_bounds__(G * CB, LP ? 4 : (G == 16 && D <= 96 ? 6 : (G == 8 
         uint2* vp = reinterpret_cast<uint2*>(Vvol + colofs + yo);
 #pragma unroll
         for (int i = 0; i < NV2; ++i) {
-          typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
           __builtin_nontemporal_store(u32x2{st[2 * i], st[2 * i + 1]}, reinterpret_cast<u32x2*>(vp + i));
         }
       } else {

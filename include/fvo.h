@@ -637,7 +637,9 @@ int fvo_timing_read(fvo_ctx* ctx, double* ms, int32_t* launches);
  * after the two retainBest passes, 6/7 PnP RANSAC per-iteration inlier counts / hypotheses of the
  * last fvo_pnp_ransac, 8 its per-frame RANSAC state: int32 best count, iteration bound, best
  * iteration, points, 9 the SGBM control words: u32 ticket, generation, L-path hand-off timeouts
- * (must stay 0), reserved, then one failure flag per pair).  For stage-by-stage parity tests only. */
+ * (must stay 0), reserved, then one failure flag per pair, 11 the disparity of the last fvo_sgbm
+ * before its median filter, int16 [pairs of the last chunk][height][width]).  For stage-by-stage
+ * parity tests only. */
 int fvo_debug_buffer(fvo_ctx* ctx, int which, void** ptr, int64_t* bytes);
 /* The first `bytes` bytes (<= the size fvo_debug_buffer reports) of that buffer copied to host
  * memory, after synchronising the context's device.  A HIP error is reported by fvo_last_error. */
