@@ -6,6 +6,7 @@ fallback — if the library or the GPU is missing, construction raises.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -97,6 +98,10 @@ SIGNATURES = {
                                                 _P, _P, _P]),
     "fvo_radius_outliers": (ctypes.c_int, [_P, _P, _L, _I, ctypes.c_double, ctypes.c_double, _P, _L, _P, _P, _P, _P]),
     "fvo_select_points": (ctypes.c_int, [_P, _P, _L, _P, _P, _P, _P, _P]),
+    "fvo_normals_workspace_bytes": (ctypes.c_int64, [_L, _I]),
+    "fvo_estimate_normals": (ctypes.c_int, [_P, _P, _L, _I, ctypes.c_double, ctypes.c_double, _I, _P, _L, _P, _I, _P,
+                                            _P, _P, _P, _P]),
+    "fvo_orient_normals": (ctypes.c_int, [_P, _P, _P, _L, _I, ctypes.POINTER(ctypes.c_double), _P]),
     "fvo_speckle_workspace_bytes": (ctypes.c_int64, [_I, _I, _I]),
     "fvo_filter_speckles": (ctypes.c_int, [_P, _P, _I, _I, _I, _L, _I, _I, _I, _I, _P, _L, _P]),
     "fvo_dense_workspace_bytes": (ctypes.c_int64, [_I, _I, _I, _I]),
@@ -717,6 +722,71 @@ class Context:
         self._check(self.L.fvo_select_points(self.h, _ptr(points), n, _ptr(keep), _ptr(out64), _ptr(out32),
                                              _ptr(n_out), _stream(self.device)))
         return out64, out32, n_out
+
+    def normals_workspace_bytes(self, n_points: int, max_nn: int = 30) -> int:
+        """fvo_normals_workspace_bytes: scratch bytes of estimate_normals."""
+        wb = int(self.L.fvo_normals_workspace_bytes(int(n_points), int(max_nn)))
+        if wb < 0:
+            raise ValueError(f"estimate_normals: unsupported size n_points={n_points} max_nn={max_nn}")
+        return wb
+
+    def estimate_normals(self, points, max_nn=30, radius=math.inf, cell=None, max_rings=2, prior=None,
+                         covariances=False, n_neighbors=False, workspace=None):
+        """Open3D estimate_normals / estimate_covariances with KDTreeSearchParamKNN(max_nn) (radius inf)
+        or KDTreeSearchParamHybrid(radius, max_nn) (fvo_estimate_normals; the rule: tests/normals_ref.py):
+        points f64 [N,3] (device, not modified) -> (normals f64 [N,3], covariances f64 [N,3,3] or None,
+        n_neighbors i32 [N] or None, stats i32 [2] = queries finished by the exact pass, points with
+        fewer than 3 neighbours, status i32 [1]: 1 = a cell index outside the 21-bit range or a
+        non-finite coordinate).  prior: f64 [N,3] normals whose side the result keeps; it is written in
+        place and returned as the normals.  cell (None: radius when finite, else 1.0) and max_rings
+        change the time only.  workspace: uint8 device tensor of >= normals_workspace_bytes(N, max_nn)
+        bytes, allocated here only when none is passed."""
+        if points.dtype != torch.float64 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
+            raise TypeError("estimate_normals: points must be a contiguous float64 [N, 3] tensor")
+        n = points.shape[0]
+        wb = self.normals_workspace_bytes(n, max_nn)
+        if workspace is None:
+            workspace = torch.empty((max(wb, 8),), dtype=torch.uint8, device=self.device)
+        elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < wb:
+            raise ValueError(f"estimate_normals: workspace must be a contiguous uint8 tensor of >= {wb} bytes")
+        if prior is None:
+            normals = torch.empty((n, 3), dtype=torch.float64, device=self.device)
+        elif prior.dtype != torch.float64 or prior.dim() != 2 or prior.shape[1] != 3 or prior.shape[0] < n or \
+                not prior.is_contiguous():
+            raise TypeError("estimate_normals: prior must be a contiguous float64 tensor of >= N rows of 3")
+        else:
+            normals = prior
+        radius = float(radius)
+        if cell is None:
+            cell = radius if math.isfinite(radius) else 1.0
+        cov = torch.empty((n, 3, 3), dtype=torch.float64, device=self.device) if covariances else None
+        cnt = torch.empty((n,), dtype=torch.int32, device=self.device) if n_neighbors else None
+        stats = torch.empty((2,), dtype=torch.int32, device=self.device)
+        st = torch.empty((1,), dtype=torch.int32, device=self.device)
+        self._check(self.L.fvo_estimate_normals(self.h, _ptr(points), n, int(max_nn), radius, float(cell),
+                                                int(max_rings), _ptr(workspace), workspace.numel(), _ptr(normals),
+                                                int(prior is not None), _ptr(cov), _ptr(cnt), _ptr(stats), _ptr(st),
+                                                _stream(self.device)))
+        return normals[:n], cov, cnt, stats, st
+
+    def orient_normals(self, points, normals, camera_location=None, direction=None):
+        """Open3D orient_normals_towards_camera_location(camera_location) or
+        orient_normals_to_align_with_direction(direction) (fvo_orient_normals): exactly one of the two,
+        three host numbers; points, normals f64 [N,3] (device); normals are changed in place and returned."""
+        if (camera_location is None) == (direction is None):
+            raise ValueError("orient_normals: give exactly one of camera_location and direction")
+        for t in (points, normals):
+            if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
+                raise TypeError("orient_normals: points and normals must be contiguous float64 [N, 3] tensors")
+        if normals.shape[0] != points.shape[0]:
+            raise ValueError("orient_normals: points and normals differ in length")
+        ref = [float(v) for v in (camera_location if direction is None else direction)]
+        if len(ref) != 3:
+            raise ValueError("orient_normals: camera_location / direction must have three components")
+        self._check(self.L.fvo_orient_normals(self.h, _ptr(points), _ptr(normals), points.shape[0],
+                                              0 if direction is None else 1, (ctypes.c_double * 3)(*ref),
+                                              _stream(self.device)))
+        return normals
 
     def speckle_workspace_bytes(self, batch: int, height: int, width: int) -> int:
         """fvo_speckle_workspace_bytes: scratch bytes of filter_speckles for [batch, height, width]."""

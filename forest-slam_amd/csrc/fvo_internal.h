@@ -313,6 +313,16 @@ int radius_outliers_run(fvo_ctx* ctx, const double* pts, int64_t n, int nb_point
                         void* ws, uint8_t* keep, int32_t* n_neighbors, int32_t* status, hipStream_t s);
 int select_points_run(fvo_ctx* ctx, const double* pts, int64_t n, const uint8_t* keep, double* out64, float* out32,
                       int32_t* n_out, hipStream_t s);
+// Normal and covariance estimation (normals.hip).  capi_normals.cpp validates the arguments.  ws: the
+// grid's sorted keys, the points in that order and the exact pass's list
+// (fvo_normals_workspace_bytes; the candidate lists are in LDS, so the size does not depend on max_nn).
+// ref: host double[3], read before the launch.
+int64_t normals_workspace_bytes(int64_t n);
+int estimate_normals_run(fvo_ctx* ctx, const double* pts, int64_t n, int max_nn, double radius, double cell,
+                         int max_rings, void* ws, double* normals, int has_prior, double* covariances,
+                         int32_t* n_neighbors, int32_t* stats, int32_t* status, hipStream_t s);
+int orient_normals_run(fvo_ctx* ctx, const double* pts, double* normals, int64_t n, int mode, const double* ref,
+                       hipStream_t s);
 int mono_init(fvo_ctx* ctx);
 int gather_run(fvo_ctx* ctx, const float* kp0, const float* kp1, const int32_t* matches, const int32_t* nmatch,
                int batch, int cap, float* p0, float* p1, int32_t* npts, hipStream_t s);

@@ -1,5 +1,5 @@
-// The uniform-grid cell table shared by map.hip (voxel_down_sample) and outlier.hip (the neighbour
-// searches): min bound by block partials, cell keys floor((p - vmin) / cell) packed 3x21 bits,
+// The uniform-grid cell table shared by map.hip (voxel_down_sample) and, through nn_grid.h, outlier.hip
+// and normals.hip (the neighbour searches): min bound by block partials, cell keys floor((p - vmin) / cell) packed 3x21 bits,
 // stable radix sort of (key, index) (hipcub), and for the voxel filter segment heads + exclusive scan
 // + the cell start table (the neighbour searches find a run of cells in the sorted keys directly).
 // Included by .hip files only; everything is in the anonymous namespace, so each translation unit

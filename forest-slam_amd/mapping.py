@@ -11,6 +11,9 @@ fvo_voxel_down_sample.
   counterpart): whole disparity maps back-projected and appended, optionally voxel-filtered.
 * ``PointMap.remove_statistical_outlier`` / ``remove_radius_outlier`` — Open3D's map clean-up
   (fvo_statistical_outliers, fvo_radius_outliers, fvo_select_points) on the device, in place.
+* ``PointMap.estimate_normals`` / ``estimate_covariances`` / ``orient_normals_*`` — Open3D's normal
+  estimation (fvo_estimate_normals, fvo_orient_normals): one fp64 normal per map point, kept aligned
+  with the points by the clean-up and dropped by any append.
 
 The map lives in HBM (fp64 + the float32 record), sized once; the append offset is a device
 counter, so batches append without host synchronisation."""
@@ -34,6 +37,9 @@ class PointMap:
         self._ws = None
         self._dense_ws = None
         self._ol_ws = None
+        self.normals64 = None  # [capacity, 3] f64, allocated by the first estimate_normals
+        self._has_normals = False
+        self._nm_ws = None
 
     def __len__(self) -> int:
         n = int(self.count.item())
@@ -51,6 +57,7 @@ class PointMap:
         and raises right here instead, before another batch is appended."""
         T = torch.as_tensor(np.asarray(cum, np.float64) if not isinstance(cum, torch.Tensor) else cum,
                             dtype=torch.float64).to(self.dev)
+        self._has_normals = False
         self.ctx.map_transform(points, n_points, T, self.count, self.xyz64, self.xyz32)
         if check:
             len(self)
@@ -66,6 +73,7 @@ class PointMap:
         n = P.shape[1]
         if n == 0:
             return
+        self._has_normals = False
         if self._tmp64 is None or self._tmp64.shape[0] < n:
             self._tmp64 = torch.empty((n, 3), dtype=torch.float64, device=self.dev)
             self._ws = torch.empty((int(self.ctx.L.fvo_voxel_workspace_bytes(n)),), dtype=torch.uint8,
@@ -101,6 +109,7 @@ class PointMap:
                             dtype=torch.float64).to(self.dev).reshape(-1, 4, 4)
         d3 = disp if disp.dim() == 3 else disp[None]
         B, H, W = d3.shape
+        self._has_normals = False
         wb = self.ctx.dense_workspace_bytes(B, H, W, step)
         if self._dense_ws is None or self._dense_ws.numel() < wb:
             self._dense_ws = torch.empty((wb,), dtype=torch.uint8, device=self.dev)
@@ -136,9 +145,11 @@ class PointMap:
 
     def _apply_mask(self, n: int, keep: torch.Tensor) -> torch.Tensor:
         """Compact the first n points by the u8 mask, in place through a scratch copy, keeping the
-        order; returns the kept indices (int64, device)."""
+        order, and the normals with them; returns the kept indices (int64, device)."""
         src = self.xyz64[:n].clone()
         self.ctx.select_points(src, keep, self.xyz64, self.xyz32, self.count)
+        if self._has_normals:
+            self.ctx.select_points(self.normals64[:n].clone(), keep, out64=self.normals64)
         return torch.nonzero(keep).reshape(-1)
 
     def _outlier_ws(self, n: int, nb_neighbors: int) -> torch.Tensor:
@@ -177,6 +188,83 @@ class PointMap:
             raise RuntimeError("remove_radius_outlier: cell index outside the 21-bit key range or a "
                                "non-finite coordinate")
         return self._apply_mask(n, keep)
+
+    def _search(self, name, max_nn, radius):
+        if max_nn is None:
+            raise NotImplementedError(f"{name}: a pure radius search has no bound on the neighbour count; give "
+                                      "max_nn (KDTreeSearchParamKNN or KDTreeSearchParamHybrid)")
+        n = len(self)
+        wb = self.ctx.normals_workspace_bytes(n, max_nn)
+        if self._nm_ws is None or self._nm_ws.numel() < wb:
+            self._nm_ws = torch.empty((max(wb, 8),), dtype=torch.uint8, device=self.dev)
+        return n, float("inf") if radius is None else float(radius)
+
+    def _checked(self, name, st):
+        if int(st.item()) != 0:
+            raise RuntimeError(f"{name}: cell index outside the 21-bit key range or a non-finite coordinate")
+
+    def estimate_normals(self, max_nn: int | None = 30, radius: float | None = None, cell: float | None = None,
+                         max_rings: int = 2) -> None:
+        """Open3D ``estimate_normals(KDTreeSearchParamKNN(max_nn))`` (radius None) or
+        ``KDTreeSearchParamHybrid(radius, max_nn)`` on the map: one unit normal per point in
+        ``normals64`` (the rule: tests/normals_ref.py).  A map that has normals keeps their side.
+        cell (metres; None: radius, else 1.0) and max_rings tune the search only (host sync)."""
+        n, radius = self._search("estimate_normals", max_nn, radius)
+        if self.normals64 is None:
+            self.normals64 = torch.zeros((self.capacity, 3), dtype=torch.float64, device=self.dev)
+        if n:
+            out = self.ctx.estimate_normals(self.xyz64[:n], max_nn, radius, cell, max_rings, workspace=self._nm_ws,
+                                            prior=self.normals64 if self._has_normals else None)
+            if not self._has_normals:
+                self.normals64[:n] = out[0]
+            self._checked("estimate_normals", out[4])
+        self._has_normals = True
+
+    def estimate_covariances(self, max_nn: int | None = 30, radius: float | None = None, cell: float | None = None,
+                             max_rings: int = 2) -> torch.Tensor:
+        """Open3D ``estimate_covariances`` with the same searches: f64 [n, 3, 3] (device; the identity
+        where a point has fewer than 3 neighbours).  The map's normals are not touched."""
+        n, radius = self._search("estimate_covariances", max_nn, radius)
+        if n == 0:
+            return torch.zeros((0, 3, 3), dtype=torch.float64, device=self.dev)
+        out = self.ctx.estimate_normals(self.xyz64[:n], max_nn, radius, cell, max_rings, workspace=self._nm_ws,
+                                        covariances=True)
+        self._checked("estimate_covariances", out[4])
+        return out[1]
+
+    def _orient(self, start, stop, **ref):
+        if not self._has_normals:
+            raise RuntimeError("the map has no normals: call estimate_normals first")
+        n = len(self)
+        start, stop, _ = slice(start, stop).indices(n)
+        if stop > start:
+            self.ctx.orient_normals(self.xyz64[start:stop], self.normals64[start:stop], **ref)
+
+    def orient_normals_towards_camera_location(self, camera=(0.0, 0.0, 0.0), start: int = 0, stop: int | None = None):
+        """Open3D ``orient_normals_towards_camera_location(camera)`` on the points [start, stop) (all
+        by default): a caller orients each batch of frames towards its own camera centre."""
+        self._orient(start, stop, camera_location=camera)
+
+    def orient_normals_to_align_with_direction(self, direction=(0.0, 0.0, 1.0)):
+        """Open3D ``orient_normals_to_align_with_direction(direction)`` on every point."""
+        self._orient(0, None, direction=direction)
+
+    def has_normals(self) -> bool:
+        """False until estimate_normals, and again after any append."""
+        return self._has_normals
+
+    def normals(self) -> np.ndarray:
+        """f64 [n, 3] on the host."""
+        if not self._has_normals:
+            raise RuntimeError("the map has no normals: call estimate_normals first")
+        return self.normals64[: len(self)].cpu().numpy()
+
+    def cloud32_normals(self) -> np.ndarray:
+        """f32 [n, 6]: x, y, z, normal_x, normal_y, normal_z (the PointCloud2 record of point_step 24)."""
+        n = len(self)
+        if not self._has_normals:
+            raise RuntimeError("the map has no normals: call estimate_normals first")
+        return torch.cat([self.xyz32[:n], self.normals64[:n].to(torch.float32)], dim=1).cpu().numpy()
 
     def cloud32(self) -> np.ndarray:
         return self.xyz32[: len(self)].cpu().numpy()

@@ -40,6 +40,8 @@
  *   fvo_statistical_outliers <- open3d PointCloud.remove_statistical_outlier(nb_neighbors, std_ratio)
  *   fvo_radius_outliers     <- open3d PointCloud.remove_radius_outlier(nb_points, radius)
  *   fvo_select_points       <- open3d PointCloud.select_by_index(ind) of the kept points, in order
+ *   fvo_estimate_normals    <- open3d PointCloud.estimate_normals / estimate_covariances (k-NN, hybrid search)
+ *   fvo_orient_normals      <- open3d PointCloud.orient_normals_towards_camera_location / _to_align_with_direction
  *                              (the map clean-up after voxel_down_sample; no reference counterpart)
  *   fvo_filter_speckles     <- cv2.filterSpeckles / StereoSGBM_create(speckleWindowSize=, speckleRange=)
  *   fvo_dense_map_append    <- (new) the disparity maps of a batch as one world-frame point cloud: the
@@ -498,6 +500,54 @@ int fvo_radius_outliers(fvo_ctx* ctx, const double* points, int64_t n_points, in
                         int32_t* status, fvo_stream stream);
 int fvo_select_points(fvo_ctx* ctx, const double* points, int64_t n_points, const uint8_t* keep, double* out64,
                       float* out32, int32_t* n_out, fvo_stream stream);
+
+/* Open3D PointCloud::EstimateNormals / EstimateCovariances (0.17, restated; any stage, no context
+ * workspace) with a k-NN or hybrid search on n_points fp64 xyz points (device [n][3], not
+ * modified), and OrientNormalsTowardsCameraLocation / OrientNormalsToAlignWithDirection.
+ * Specification: tests/normals_ref.py.  All arithmetic is fp64, one rounding per operation written
+ * here, d2 as above.
+ * Neighbours of i: every j in [0, n), j = i included, in the order (d2(i, j), j); the first
+ * min(max_nn, n) of them, and of those the ones with d2 < radius*radius (strict) — m_i points.
+ * radius = +inf is the plain k-NN search.  Equal d2 at the cut go to the lower index (Open3D leaves
+ * it unspecified).
+ * Covariance (utility::ComputeCovariance): the cumulants x, y, z, xx, xy, xz, yy, yz, zz summed over
+ * the neighbours in that order (cum = cum + term, term one product of raw coordinates), each
+ * divided by (double)m_i; C00 = c3 - c0*c0, C01 = c4 - c0*c1, C02 = c5 - c0*c2, C11 = c6 - c1*c1,
+ * C12 = c7 - c1*c2, C22 = c8 - c2*c2, symmetric.  m_i < 3: C = I.
+ * Normal: (0, 0, 1) when m_i < 3 or C is all zeros; else the eigenvector of C's smallest eigenvalue
+ * by a cyclic Jacobi solve: sweeps over the pairs (0,1), (0,2), (1,2); a pair with a_pq == 0 is
+ * skipped, else th = (a_qq - a_pp) / (2*a_pq), t = 1 / (|th| + sqrt(th*th + 1)) negated when th <
+ * 0, c = 1 / sqrt(t*t + 1), s = t*c, a_pp -= t*a_pq, a_qq += t*a_pq, a_pq = 0, a_rp' = c*a_rp -
+ * s*a_rq, a_rq' = s*a_rp + c*a_rq for the third index r, and the columns p, q of V (from I) rotated
+ * the same way; until the three off-diagonals are exactly 0, 10 sweeps at most.  The column of V
+ * at the smallest diagonal entry (ties: the lowest index) divided by sqrt((x*x + y*y) + z*z).
+ * has_prior != 0: normals holds a prior o_i on entry; an all-zero result becomes o_i, any other is
+ * negated when ((n.x*o.x + n.y*o.y) + n.z*o.z) < 0.
+ * The search walks fvo_statistical_outliers' grid (cell, max_rings: the time only, never a
+ * result); a query is finished once the visited cube's nearest face is radius away, whatever it
+ * holds, so a hybrid search with cell ~ radius leaves nothing to the brute-force pass.
+ * workspace:   device scratch of fvo_normals_workspace_bytes(n_points, max_nn) bytes (caller-owned,
+ *              8-byte aligned, needs no clearing between calls); -1 for a refused size.
+ * normals:     device [n][3], written at every point (read first when has_prior).
+ * covariances: device [n][9] (row-major 3x3) or NULL.  n_neighbors: device [n] (m_i) or NULL.
+ * stats:       device int32[2]: queries finished by the brute-force pass, points with m_i < 3.
+ * status (device, may be NULL): 0 ok, 1 = a cell index outside [0, 2^21) or a non-finite
+ *              coordinate (every result invalid).
+ * fvo_orient_normals: ref is a host double[3], read before the call returns.  mode 0: ref is the
+ * camera location c, r_i = c - p_i; mode 1: ref is a direction, r_i = ref (not all zeros).  A normal
+ * with all components 0 becomes r_i / sqrt((x*x + y*y) + z*z), or (0, 0, 1) when r_i is all zeros;
+ * any other is negated when ((n.x*r.x + n.y*r.y) + n.z*r.z) < 0.
+ * n_points == 0 returns 0 after the argument checks (stats is zeroed).  Nothing is allocated; the
+ * calls are stream-ordered and can be captured into a hipGraph; their launches are not in the
+ * fvo_timing_* table. */
+#define FVO_NORMALS_MAX_NN 64
+int64_t fvo_normals_workspace_bytes(int64_t n_points, int32_t max_nn);
+int fvo_estimate_normals(fvo_ctx* ctx, const double* points, int64_t n_points, int32_t max_nn, double radius,
+                         double cell, int32_t max_rings, void* workspace, int64_t workspace_bytes, double* normals,
+                         int32_t has_prior, double* covariances, int32_t* n_neighbors, int32_t* stats,
+                         int32_t* status, fvo_stream stream);
+int fvo_orient_normals(fvo_ctx* ctx, const double* points, double* normals, int64_t n_points, int32_t mode,
+                       const double* ref, fvo_stream stream);
 
 /* cv2.filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) on `batch` CV_16SC1 disparity maps, in
  * place (any stage; any image size, not tied to the context's).  Two 4-neighbours are connected
