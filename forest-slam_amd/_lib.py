@@ -102,6 +102,11 @@ SIGNATURES = {
     "fvo_estimate_normals": (ctypes.c_int, [_P, _P, _L, _I, ctypes.c_double, ctypes.c_double, _I, _P, _L, _P, _I, _P,
                                             _P, _P, _P, _P]),
     "fvo_orient_normals": (ctypes.c_int, [_P, _P, _P, _L, _I, ctypes.POINTER(ctypes.c_double), _P]),
+    "fvo_icp_workspace_bytes": (ctypes.c_int64, [_L, _L]),
+    "fvo_registration_icp": (ctypes.c_int, [_P, _P, _L, _P, _P, _L, ctypes.c_double, ctypes.c_double,
+                                            ctypes.POINTER(ctypes.c_double), _I, ctypes.c_double, ctypes.c_double, _I,
+                                            _P, _L, _P, _P, _P, _P, _P]),
+    "fvo_transform_points": (ctypes.c_int, [_P, _P, _P, _P, _L, ctypes.POINTER(ctypes.c_double), _P]),
     "fvo_speckle_workspace_bytes": (ctypes.c_int64, [_I, _I, _I]),
     "fvo_filter_speckles": (ctypes.c_int, [_P, _P, _I, _I, _I, _L, _I, _I, _I, _I, _P, _L, _P]),
     "fvo_dense_workspace_bytes": (ctypes.c_int64, [_I, _I, _I, _I]),
@@ -787,6 +792,68 @@ class Context:
                                               0 if direction is None else 1, (ctypes.c_double * 3)(*ref),
                                               _stream(self.device)))
         return normals
+
+    def icp_workspace_bytes(self, n_source: int, n_target: int) -> int:
+        """fvo_icp_workspace_bytes: scratch bytes of registration_icp."""
+        wb = int(self.L.fvo_icp_workspace_bytes(int(n_source), int(n_target)))
+        if wb < 0:
+            raise ValueError(f"registration_icp: unsupported size n_source={n_source} n_target={n_target}")
+        return wb
+
+    def registration_icp(self, source, target, max_correspondence_distance, init=None, estimation=0,
+                         target_normals=None, relative_fitness=1e-6, relative_rmse=1e-6, max_iteration=30, cell=None,
+                         workspace=None, sums=False, correspondences=True):
+        """Open3D registration_icp (max_iteration 0: evaluate_registration) of source onto target
+        (fvo_registration_icp; the rule: tests/icp_ref.py): f64 [N,3] device tensors, not modified;
+        estimation 0 point-to-point, 1 point-to-plane (target_normals f64 [Nt,3]); init: 4x4 host numbers
+        (None: the identity) -> (result f64 [20] = T row-major, fitness, inlier_rmse, correspondences,
+        iterations; sums f64 [45] or None: the last pass's 28 sums, m and the T that entered it;
+        correspondences i32 [N] or None: the target index or -1; status i32 [1]: bit 1 = a target cell
+        index outside the 21-bit range or a non-finite coordinate, bit 2 = a degenerate system).
+        Everything stays on the device: the call does not synchronise.  cell None = the distance.
+        workspace: uint8 device tensor of >= icp_workspace_bytes(N, Nt) bytes, allocated here only when
+        none is passed."""
+        for t, name in ((source, "source"), (target, "target"), (target_normals, "target_normals")):
+            if t is not None and (t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous()):
+                raise TypeError(f"registration_icp: {name} must be a contiguous float64 [N, 3] tensor")
+        ns, nt = source.shape[0], target.shape[0]
+        if target_normals is not None and target_normals.shape[0] < nt:
+            raise ValueError("registration_icp: target_normals has fewer rows than target")
+        wb = self.icp_workspace_bytes(ns, nt)
+        if workspace is None:
+            workspace = torch.empty((max(wb, 8),), dtype=torch.uint8, device=self.device)
+        elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < wb:
+            raise ValueError(f"registration_icp: workspace must be a contiguous uint8 tensor of >= {wb} bytes")
+        T = [float(v) for v in (np.eye(4) if init is None else np.asarray(init, np.float64)).reshape(-1)]
+        if len(T) != 16:
+            raise ValueError("registration_icp: init must be a 4x4 matrix")
+        r = float(max_correspondence_distance)
+        result = torch.empty((20,), dtype=torch.float64, device=self.device)
+        sm = torch.empty((45,), dtype=torch.float64, device=self.device) if sums else None
+        corr = torch.empty((ns,), dtype=torch.int32, device=self.device) if correspondences else None
+        st = torch.empty((1,), dtype=torch.int32, device=self.device)
+        self._check(self.L.fvo_registration_icp(self.h, _ptr(source), ns, _ptr(target), _ptr(target_normals), nt, r,
+                                                float(r if cell is None else cell), (ctypes.c_double * 16)(*T),
+                                                int(estimation), float(relative_fitness), float(relative_rmse),
+                                                int(max_iteration), _ptr(workspace), workspace.numel(), _ptr(result),
+                                                _ptr(sm), _ptr(corr), _ptr(st), _stream(self.device)))
+        return result, sm, corr, st
+
+    def transform_points(self, points, T, points32=None, normals=None):
+        """Open3D PointCloud.transform (fvo_transform_points): points f64 [N,3] (device) become
+        ((r00*x + r01*y) + r02*z) + t0 ... in place; points32 f32 [N,3] receives their casts, normals
+        f64 [N,3] are rotated in place.  T: 4x4 host numbers.  Returns points."""
+        for t, dt in ((points, torch.float64), (points32, torch.float32), (normals, torch.float64)):
+            if t is not None and (t.dtype != dt or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous() or
+                                  t.shape[0] < points.shape[0]):
+                raise TypeError("transform_points: points, points32 and normals must be contiguous [N, 3] tensors "
+                                "(float64, float32, float64)")
+        M = [float(v) for v in np.asarray(T, np.float64).reshape(-1)]
+        if len(M) != 16:
+            raise ValueError("transform_points: T must be a 4x4 matrix")
+        self._check(self.L.fvo_transform_points(self.h, _ptr(points), _ptr(points32), _ptr(normals), points.shape[0],
+                                                (ctypes.c_double * 16)(*M), _stream(self.device)))
+        return points
 
     def speckle_workspace_bytes(self, batch: int, height: int, width: int) -> int:
         """fvo_speckle_workspace_bytes: scratch bytes of filter_speckles for [batch, height, width]."""

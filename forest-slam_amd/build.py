@@ -20,7 +20,7 @@ OBJ = os.path.join(HERE, "build", "obj")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 SOURCES = ["capi.cpp", "orb.hip", "bf.hip", "sgbm.hip", "pose.hip", "ba.hip", "essential.hip", "ingest.hip", "map.hip", "util.hip",
            "speckle.hip", "dense.hip", "capi_rectify.cpp", "rectify.hip", "capi_stereo.cpp", "sparse_stereo.hip",
-           "capi_outlier.cpp", "outlier.hip", "capi_normals.cpp", "normals.hip"]
+           "capi_outlier.cpp", "outlier.hip", "capi_normals.cpp", "normals.hip", "capi_icp.cpp", "icp.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wno-unused-result", "-Wno-unused-function", "-Wno-unused-variable"]

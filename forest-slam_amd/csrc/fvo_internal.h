@@ -323,6 +323,19 @@ int estimate_normals_run(fvo_ctx* ctx, const double* pts, int64_t n, int max_nn,
                          int32_t* n_neighbors, int32_t* stats, int32_t* status, hipStream_t s);
 int orient_normals_run(fvo_ctx* ctx, const double* pts, double* normals, int64_t n, int mode, const double* ref,
                        hipStream_t s);
+// ICP registration (icp.hip).  capi_icp.cpp validates the arguments.  ws: the target's grid (sorted
+// keys, points and normals in that order), the source's order, one row of partial sums per block of
+// 256 source points and the call's state (fvo_icp_workspace_bytes).  init / T: host double[16], read
+// before the first launch.  icp_trivial_run: the result of an empty source or target (no search).
+int64_t icp_workspace_bytes(int64_t n_source, int64_t n_target);
+int registration_icp_run(fvo_ctx* ctx, const double* source, int64_t ns, const double* target,
+                         const double* target_normals, int64_t nt, double radius, double cell, const double* init,
+                         int estimation, double rel_fitness, double rel_rmse, int max_iteration, void* ws,
+                         double* result, double* sums, int32_t* correspondences, int32_t* status, hipStream_t s);
+int icp_trivial_run(fvo_ctx* ctx, const double* init, int64_t ns, double* result, double* sums,
+                    int32_t* correspondences, int32_t* status, hipStream_t s);
+int transform_points_run(fvo_ctx* ctx, double* points, float* points32, double* normals, int64_t n, const double* T,
+                         hipStream_t s);
 int mono_init(fvo_ctx* ctx);
 int gather_run(fvo_ctx* ctx, const float* kp0, const float* kp1, const int32_t* matches, const int32_t* nmatch,
                int batch, int cap, float* p0, float* p1, int32_t* npts, hipStream_t s);

@@ -14,6 +14,9 @@ fvo_voxel_down_sample.
 * ``PointMap.estimate_normals`` / ``estimate_covariances`` / ``orient_normals_*`` — Open3D's normal
   estimation (fvo_estimate_normals, fvo_orient_normals): one fp64 normal per map point, kept aligned
   with the points by the clean-up and dropped by any append.
+* ``PointMap.transform`` / ``registration_icp`` — Open3D's ``transform(T)`` in place (fvo_transform_points;
+  the normals are rotated and kept) and ICP of this map onto another (fvo_registration_icp through
+  ``registration.registration_icp``).
 
 The map lives in HBM (fp64 + the float32 record), sized once; the append offset is a device
 counter, so batches append without host synchronisation."""
@@ -248,6 +251,22 @@ class PointMap:
     def orient_normals_to_align_with_direction(self, direction=(0.0, 0.0, 1.0)):
         """Open3D ``orient_normals_to_align_with_direction(direction)`` on every point."""
         self._orient(0, None, direction=direction)
+
+    def transform(self, T) -> "PointMap":
+        """Open3D ``transform(T)`` on the map, in place (fvo_transform_points): every point becomes T p in
+        fp64 (the expression of tests/icp_ref.py), the float32 record is its cast, the normals are
+        rotated and kept.  T: 4x4 host numbers, bottom row (0, 0, 0, 1).  Host sync (the length)."""
+        n = len(self)
+        self.ctx.transform_points(self.xyz64[:n], T, self.xyz32[:n], self.normals64[:n] if self._has_normals else None)
+        return self
+
+    def registration_icp(self, target, max_correspondence_distance, init=None, estimation_method=None, criteria=None,
+                         **kw):
+        """Open3D ``registration_icp(self, target, ...)``: this map as the source; see
+        ``registration.registration_icp``.  Point-to-plane needs ``target.has_normals()``."""
+        from . import registration
+        return registration.registration_icp(self, target, max_correspondence_distance, init, estimation_method,
+                                             criteria, **kw)
 
     def has_normals(self) -> bool:
         """False until estimate_normals, and again after any append."""

@@ -42,6 +42,9 @@
  *   fvo_select_points       <- open3d PointCloud.select_by_index(ind) of the kept points, in order
  *   fvo_estimate_normals    <- open3d PointCloud.estimate_normals / estimate_covariances (k-NN, hybrid search)
  *   fvo_orient_normals      <- open3d PointCloud.orient_normals_towards_camera_location / _to_align_with_direction
+ *   fvo_registration_icp    <- open3d pipelines.registration.registration_icp / evaluate_registration
+ *                              (TransformationEstimationPointToPoint / PointToPlane)
+ *   fvo_transform_points    <- open3d PointCloud.transform(T)
  *                              (the map clean-up after voxel_down_sample; no reference counterpart)
  *   fvo_filter_speckles     <- cv2.filterSpeckles / StereoSGBM_create(speckleWindowSize=, speckleRange=)
  *   fvo_dense_map_append    <- (new) the disparity maps of a batch as one world-frame point cloud: the
@@ -548,6 +551,69 @@ int fvo_estimate_normals(fvo_ctx* ctx, const double* points, int64_t n_points, i
                          int32_t* status, fvo_stream stream);
 int fvo_orient_normals(fvo_ctx* ctx, const double* points, double* normals, int64_t n_points, int32_t mode,
                        const double* ref, fvo_stream stream);
+
+/* Open3D pipelines::registration::RegistrationICP / EvaluateRegistration (0.17, restated; any stage,
+ * no context workspace) of n_source fp64 xyz points onto n_target (device [n][3], not modified), and
+ * PointCloud::Transform.  Specification: tests/icp_ref.py.  All arithmetic is fp64, one rounding per
+ * operation written here.
+ * Transform: s' = T s, always of the original source (Open3D transforms the cloud incrementally and
+ * accumulates the roundings), x' = ((r00*x + r01*y) + r02*z) + t0 and likewise y', z'.
+ * Correspondence of source i (KDTreeFlann::SearchHybrid(s', r, 1), r = max_correspondence_distance):
+ * the target index j that minimises (d2(s'_i, t_j), j), d2 as above with dx = t.x - s'.x; kept iff d2 <
+ * r*r (strict), else -1; equal d2 go to the lower index.  m kept: fitness = m / n_source, inlier_rmse =
+ * sqrt(sum d2 / m), 0 when m = 0.
+ * Sums: with the pivot c = the target's per-axis minimum, p = s' - c, q = t - c, n the target's normal:
+ *   point-to-plane (1): d = p - q, r = ((d.x*n.x + d.y*n.y) + d.z*n.z), J = [p x n, n]; [0..20] the upper
+ *     triangle of sum J J^T row by row, [21..26] sum J_a*r, [27] sum d2.  A x = -b by a 6x6 LDL^T (D_j =
+ *     A_jj - sum_{k<j} (L_jk*L_jk)*D_k, L_ij = (A_ji - sum_{k<j} (L_ik*L_jk)*D_k) / D_j, y_i = rhs_i -
+ *     sum_{k<i} L_ik*y_k, x_i = y_i / D_i - sum_{k>i} L_ki*x_k, every sum one subtraction per term in
+ *     ascending k), x = (w, v); R = I + (2 / (1 + g.g)) (G + G G) with the Gibbs vector g = w / 2, G = [g]x,
+ *     G G = g g^T - (g.g) I (Open3D composes Euler angles: the same to O(|w|^3), the same fixed point).
+ *     A pivot that is not > 0 and finite, or m = 0: the identity update and status bit 2.
+ *   point-to-point (0): [0..2] sum p, [3..5] sum q, [6..14] sum p_a*q_b row by row, [27] sum d2.  Horn's
+ *     closed form (Open3D's Umeyama without scale): pm = sum p / m, qm = sum q / m, M_ab = sum p_a q_b / m
+ *     - pm_a*qm_b, the symmetric 4x4 N(M) (N00 = (Mxx + Myy) + Mzz, N11 = (Mxx - Myy) - Mzz, N22 = (Myy -
+ *     Mxx) - Mzz, N33 = (Mzz - Mxx) - Myy, N01 = Myz - Mzy, N02 = Mzx - Mxz, N03 = Mxy - Myx, N12 = Mxy +
+ *     Myx, N13 = Mzx + Mxz, N23 = Myz + Mzy), the eigenvector of its largest diagonal entry (ties: the
+ *     lowest index) after fvo_estimate_normals' cyclic Jacobi over the pairs (0,1), (0,2), (0,3), (1,2),
+ *     (1,3), (2,3) until the six off-diagonals are exactly 0, 12 sweeps at most; the quaternion (w, x, y,
+ *     z) divided by sqrt(((w*w + x*x) + y*y) + z*z), R from it, v = qm - R pm.  m = 0: as above.
+ *   The update is x -> c + R (x - c) + v: U = [R | (v + c) - R c], T <- U T, bottom row (0, 0, 0, 1).
+ *   The device sums the terms by a fixed tree (the same bits on every call); the specification's
+ *   math.fsum differs from it by at most 2 m 2^-53 sum |term|.
+ * Loop: evaluate at init; up to max_iteration times: update, evaluate, stop when |d fitness| <
+ * relative_fitness and |d inlier_rmse| < relative_rmse.  max_iteration = 0 is evaluate_registration;
+ * max_iteration + 1 passes of two launches are enqueued and skip themselves once the loop has stopped:
+ * no host synchronisation.  The search walks fvo_radius_outliers' grid built on the target (cell: the
+ * time only, never a result; max_correspondence_distance / cell > 8 is refused).
+ * init:      host double[16], row-major, read before the call returns; finite, bottom row (0, 0, 0, 1).
+ * target_normals: device [n_target][3], NULL unless estimation is 1.
+ * workspace: device scratch of fvo_icp_workspace_bytes(n_source, n_target) bytes (caller-owned, 8-byte
+ *            aligned, needs no clearing between calls); that function returns -1 for a refused size.
+ * result:    device double[20]: T (row-major), fitness, inlier_rmse, the number of correspondences,
+ *            iterations (the updates applied; an identity update counts).
+ * sums:      device double[FVO_ICP_SUMS] or NULL: the last pass's 28 sums, m, and the T that entered it.
+ * correspondences: device int32[n_source] or NULL, for the final T.
+ * status (device, may be NULL): bit 1 = a target cell index outside [0, 2^21) or a non-finite
+ *            coordinate (every result invalid), bit 2 = a degenerate system (identity update applied).
+ * n_source == 0 or n_target == 0 (after the argument checks): result holds init, fitness 0, every
+ * correspondence -1; no search is launched and workspace may be NULL.
+ * fvo_transform_points: the transform expression above on points (device [n][3], in place); points32
+ * (device float [n][3] or NULL) receives the float32 casts, normals (device [n][3] or NULL) are rotated
+ * in place, ((r00*x + r01*y) + r02*z).  T: host double[16] as init.
+ * Nothing is allocated; the calls are stream-ordered and can be captured into a hipGraph; their
+ * launches are not in the fvo_timing_* table. */
+#define FVO_ICP_MAX_ITERATION 1000
+#define FVO_ICP_SUMS 45
+int64_t fvo_icp_workspace_bytes(int64_t n_source, int64_t n_target);
+int fvo_registration_icp(fvo_ctx* ctx, const double* source, int64_t n_source, const double* target,
+                         const double* target_normals, int64_t n_target, double max_correspondence_distance,
+                         double cell, const double* init, int32_t estimation, double relative_fitness,
+                         double relative_rmse, int32_t max_iteration, void* workspace, int64_t workspace_bytes,
+                         double* result, double* sums, int32_t* correspondences, int32_t* status,
+                         fvo_stream stream);
+int fvo_transform_points(fvo_ctx* ctx, double* points, float* points32, double* normals, int64_t n_points,
+                         const double* T, fvo_stream stream);
 
 /* cv2.filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) on `batch` CV_16SC1 disparity maps, in
  * place (any stage; any image size, not tied to the context's).  Two 4-neighbours are connected
